@@ -2,7 +2,12 @@
 """Headline benchmark: training cells/sec of JAMIE's two-modality coupled VAE on MI355X
 (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c5dims] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c5dims] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line.
+Everything else it can measure -- the roofline block and per-kernel event timings, the steady-state figure, the fp32 record,
+the other configurations, the CPU baseline and, at N > 1, the RCCL account, the exchange's exposed wait, the all-reduce probe
+and the other data-parallel arrangements -- runs behind --full only.
 
 N > 1 runs one rank per GPU.  Either a launcher starts the ranks,
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -507,6 +512,28 @@ def rccl_record(world, log_dir):
     return rec
 
 
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: the parameters are written whole up to this many elements, else this fixed sample
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, model, eng):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files (numbers of equal runs of
+    two builds can be compared file by file):
+      losses.npy      float64 [5]: the step's KL, reconstruction, cosine and F losses (weighted, as read_losses()) and their total
+      parameters.npy  float32: the model's state after the step -- every floating-point tensor of state_dict() (reference names
+                      and shapes, no padding: weights, biases, sigma, BatchNorm running statistics), flattened in state_dict()
+                      order and concatenated; beyond DUMP_SAMPLE elements the DUMP_SAMPLE positions that
+                      default_rng(DUMP_SEED) draws without replacement, in ascending order (16 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ls, total, _ = eng.read_losses()
+    np.save(os.path.join(out_dir, 'losses.npy'), np.array(list(ls) + [total], dtype=np.float64))
+    flat = torch.cat([t.reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+    if flat.numel() > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(pick).to(flat.device)]
+    np.save(os.path.join(out_dir, 'parameters.npy'), flat.cpu().numpy().astype(np.float32))
+
+
 def visible_gpus(root='/sys/class/kfd/kfd/topology/nodes'):
     """GPUs visible to this process, counted WITHOUT a HIP call (the launcher parent must never initialise the runtime: it
     fork+execs the ranks): KFD's topology nodes with SIMDs, cut down by HIP_/ROCR_/CUDA_VISIBLE_DEVICES when those hold plain
@@ -640,6 +667,14 @@ def main():
     ap.add_argument('--tune', default=os.environ.get('JAMIE_TUNE', ''),
                     help='A/B measurements (tools/ab.sh): "key=value+key=value" for jamie_amd.engine.tune() -- tile / split-K plans and the '
                          'older variant of every adopted change (engine.TUNING); also read from JAMIE_TUNE')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: roofline and per-kernel event timings, `steady_state`, the fp32 record, '
+                         '`other_configs`, the CPU baseline; at N > 1 the RCCL account, the exchange\'s exposed wait, the all-reduce '
+                         'probe and the other data-parallel arrangements (the --no-* options above trim it).  Off: set up, warm up, '
+                         'time --steps steps, write --dump-outputs, print the line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (its losses, the parameters after it) as '
+                         'DIR/<name>.npy (dump_outputs)')
     args = ap.parse_args()
     if args.dtype is None:
         args.dtype = DEFAULT_DTYPE.get(args.config, 'bf16')
@@ -651,7 +686,7 @@ def main():
 
     # RCCL's own account of the communicator it builds (read back into the JSON line at N > 1): init-time log only
     log_dir = None
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1 and 'NCCL_DEBUG' not in os.environ:
+    if args.full and int(os.environ.get('WORLD_SIZE', '1')) > 1 and 'NCCL_DEBUG' not in os.environ:
         import tempfile
         log_dir = tempfile.mkdtemp(prefix='jamie_rccl_')
         os.environ.update(NCCL_DEBUG='INFO', NCCL_DEBUG_SUBSYS='INIT,GRAPH',
@@ -745,7 +780,8 @@ def main():
             eng_.enable_pipeline(args.opt_priority)
         if args.side_transposes:
             eng_.enable_side_transposes()
-        eng_.enable_kernel_timing('enc_gemm', 'enc0_gemm', 'adam')
+        if args.full:
+            eng_.enable_kernel_timing('enc_gemm', 'enc0_gemm', 'adam')
         # the step is a fixed launch sequence on static buffers: record it once, replay it (one foreign call per launch)
         plan_ = eng_.make_plan(data_, idx_, hi - lo, rep, ar_, prefetch=args.prefetch)
         # --settle N (default 0): N more untimed replays.  Round 4 ran 100 of them by default in front of the driver's W = 5; the
@@ -793,9 +829,10 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    if world > 1 and allreduce is not None and hasattr(allreduce, 'enable_exposure'):
+    if args.full and world > 1 and allreduce is not None and hasattr(allreduce, 'enable_exposure'):
         allreduce.enable_exposure(True, every=4)      # HIP events around finish()'s device-side waits (the exposed part of the exchange)
-    events = os.environ.get('JAMIE_BENCH_NO_EVENTS') != '1'
+    # (a plain run records no event in the timed region: the events serve the roofline block, which --full adds)
+    events = args.full and os.environ.get('JAMIE_BENCH_NO_EVENTS') != '1'
     if events:
         # drop the warm-up samples.  In the timed region only the two launches the roofline block needs are bracketed, on every 8th
         # step (every 4th of a run under 16 steps): an event between two launches costs the step ~3 us (it ends the back-to-back
@@ -815,8 +852,13 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        eng.flush(collective=True)          # (every rank: the optimiser's results in the replicated buffers)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, eng)
     exposure, msg_elems = None, []
-    if world > 1 and allreduce is not None and hasattr(allreduce, 'exposed_us'):
+    if args.full and world > 1 and allreduce is not None and hasattr(allreduce, 'exposed_us'):
         exposure = allreduce.exposed_us()
         msg_elems = allreduce.message_elements()
         allreduce.enable_exposure(False)
@@ -825,7 +867,7 @@ def main():
     # never `value`.
     steady = None
     timing_head = {k: eng.kernel_timing_ms(k, 'all') for k in head_labels} if events else None
-    if args.dry_run_world <= 1:
+    if args.full and args.dry_run_world <= 1:
         if events:
             eng.enable_kernel_timing('enc_gemm', 'enc0_gemm', 'adam', every=25)     # (this leg's own samples: 8 of 200 steps)
         barrier()
@@ -844,7 +886,7 @@ def main():
             steady['kernel_event_timing_ms'] = {k: eng.kernel_timing_ms(k, 'all') for k in ('enc_gemm', 'enc0_gemm', 'adam')}
             if timing_head is not None and 'enc_gemm' not in timing_head:
                 timing_head['enc_gemm'] = steady['kernel_event_timing_ms']['enc_gemm']      # (bf16: bracketed in the steady-state leg only)
-    if not events:          # kernel timings from extra steps AFTER the timed region -- on every rank (a step is a collective)
+    if args.full and not events:          # kernel timings from extra steps AFTER the timed region -- on every rank (a step is a collective)
         eng.enable_kernel_timing('enc_gemm', 'enc0_gemm', 'adam')
         for _ in range(20):
             step()
@@ -890,7 +932,8 @@ def main():
                       'fp32_messages' if comm is not None else 'bf16_messages')
         del p1, e1, m1
 
-    if rank == 0:
+    def roofline_block():
+        """(roofline, kernel_event_timing_ms) of the line (--full)."""
         # roofline of the dominant kernel (DESIGN.md §5):
         #   f32 : the d <-> 2d Linear forward GEMM launch (both modalities grouped; 4 launches per step, each
         #         4*B*sum(d^2) FLOP) against the exact-fp32 MFMA peak;
@@ -944,6 +987,9 @@ def main():
                     'whole_step_frac_on_fp32_byte_model_44P': (step_bytes_f32_model * cells_s / world / B) / (PEAK_HBM_GBS * 1e9),
                     'gemm_bf16_tflops': gemm_flop / (gemm_ms * 1e-3) / 1e12, 'gemm_avg_launch_ms': gemm_ms,
                     'encoder_gemm': enc0}
+        return roof, timing_detail
+
+    if rank == 0:
         out = {
             'metric': 'training cells/sec (two-modality coupled VAE)', 'value': cells_s, 'unit': 'cells/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps,
@@ -959,10 +1005,10 @@ def main():
                        'dp_optimizer': dp_opt, **({'dp_optimizer_fallback': dp_fallback} if dp_fallback else {}),
                        'parameters': model.num_parameters(),
                        'flop_per_cell': flops_per_cell(dims, L)},
-            'roofline': roof,
-            'kernel_event_timing_ms': timing_detail,
-            'final_loss': total,
         }
+        if args.full:
+            out['roofline'], out['kernel_event_timing_ms'] = roofline_block()
+        out['final_loss'] = total
         if steady is not None:
             out['steady_state'] = steady
         if trace_ev:
@@ -972,7 +1018,7 @@ def main():
             out['dry_run_world'] = args.dry_run_world
             out['dp_model'] = dp
             out['metric'] += f' [DRY RUN: per-rank compute path of a {args.dry_run_world}-rank step, collectives skipped; not a benchmark line]'
-        if world > 1:
+        if args.full and world > 1:
             out['rccl'] = rccl_record(world, log_dir) if log_dir else {'backend': torch.distributed.get_backend(),
                                                                         'world': torch.distributed.get_world_size(), 'algo': None}
             # measured, not modelled: the time the step's stream stood still in finish() waiting for messages on the wire
@@ -980,7 +1026,7 @@ def main():
                                'messages_per_step': [{'elements': int(n), 'bytes': int(n) * (2 if comm is not None else 4)} for n in msg_elems],
                                'note': 'HIP events on the launch stream around the device-side waits of finish(), every 4th timed step '
                                        '(median / mean / max in us); messages in issue order'}
-    if world > 1:
+    if args.full and world > 1:
         # every rank: all-reduce bandwidth of this communicator at the step's message sizes (the headline is already measured)
         try:
             probe = allreduce_probe(msg_elems, dev, world)
@@ -988,7 +1034,7 @@ def main():
             probe = {'error': f'{type(err).__name__}: {err}'[:300]}
         if rank == 0:
             out['rccl']['allreduce_probe'] = probe
-    if world > 1 and not args.no_f32_record:
+    if args.full and world > 1 and not args.no_f32_record:
         # N > 1: the same job in its other data-parallel arrangements, timed right behind the headline on every rank (a step is
         # a collective), so that one invocation reports them all:
         #   grad_comm_f32       (bf16 compute, bf16 messages in the headline) fp32 gradient messages: exact sums, twice the bytes
@@ -1055,7 +1101,7 @@ def main():
                     out[key] = {'value': None, 'error': f'{type(err).__name__}: {err}'[:300]}
             finally:
                 watchdog.cancel()
-    if world == 1:
+    if args.full and world == 1:
         # free the timed engine's buffers before the side legs
         del plan
         if args.dtype == 'bf16' and not args.no_f32_record and len(dims) == 2 and not any(d % 8 for d in dims):

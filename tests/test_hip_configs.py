@@ -77,6 +77,49 @@ def _clone_state(P, Bf):
     return P2, {k: v.clone() for k, v in Bf.items()}
 
 
+def _float64(P, Bf, X, noise):
+    """The oracle's state, batch and noise in float64 (the same values).  A float64 step is a yardstick whose own rounding is
+    far below the fp32 tolerances; an fp32 CPU step is not: at config 4 its decoders.0.0.weight gradient is 3.6e-3 (relative
+    L2) from the float64 step when torch splits the reductions over 8 or 16 threads and 1e-6 on one thread."""
+    P64 = {k: v.detach().double().requires_grad_(True) for k, v in P.items()}
+    Bf64 = {k: v.double() if v.is_floating_point() else v.clone() for k, v in Bf.items()}
+    n64 = {k: [[None if m is None else m.double() for m in v] if isinstance(v, list) else v.double() for v in vs]
+           for k, vs in noise.items()}
+    return P64, Bf64, [x.double() for x in X], n64
+
+
+KINK_BAND = 1e-5       # fp32 rounding of a LeakyReLU input (BatchNorm output, O(1)): at most 4e-6 at config 4 (fp32 CPU step vs float64)
+
+
+def _kink_rows(P, X, combined, noise, p):
+    """Rows whose gradient is not defined to fp32 precision: a LeakyReLU input that the float64 step puts within KINK_BAND of the
+    kink (and that dropout keeps) takes either branch in a correct fp32 implementation -- slope 1 or 0.01 for that element, i.e.
+    a different gradient for its column's Linear row and bias and BatchNorm weight and bias.  (Config 4: one input at 2e-11 in
+    decoders.0.1 moves decoders.0.0.weight by 3.6e-3 in relative L2 between the fp32 and the float64 step.)  From the
+    pre-step float64 state `P`, the batch, the decoders' inputs `combined` and the noise: {parameter name: row indices}."""
+    rows = {}
+    for i in range(len(X)):
+        for a, pre, masks in ((X[i], f'encoders.{i}', noise['enc_masks'][i]), (combined[i], f'decoders.{i}', noise['dec_masks'][i])):
+            for (lin, bn), mask in zip(((0, 1), (4, 5)), masks):
+                y = torch.nn.functional.batch_norm(orc.linear(P, f'{pre}.{lin}', a), None, None, P[f'{pre}.{bn}.weight'],
+                                                   P[f'{pre}.{bn}.bias'], training=True, eps=orc.BN_EPS)
+                near = (y.abs() < KINK_BAND) & ((mask > 0) if mask is not None else True)
+                cols = sorted(set(near.nonzero()[:, 1].tolist()))
+                if cols:
+                    for name in (f'{pre}.{lin}.weight', f'{pre}.{lin}.bias', f'{pre}.{bn}.weight', f'{pre}.{bn}.bias'):
+                        rows[name] = cols
+                a = torch.nn.functional.leaky_relu(y, orc.LRELU_SLOPE)
+                if mask is not None and p > 0:
+                    a = a * (mask / (1 - p))
+    return rows
+
+
+def _drop_rows(t, rows):
+    keep = np.ones(t.shape[0], dtype=bool)
+    keep[rows] = False
+    return t[keep]
+
+
 def _rel(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
 
@@ -383,16 +426,21 @@ def test_config4_full_size_step_vs_generalised_oracle(jam, mode):
     B = 512, dropout 0.6.  The reference asserts two modalities (jamie.py:420), so the oracle is the build-defined
     generalisation (reduces to the reference for M = 2, tests/test_oracle_golden.py).  fp32: losses,
     every gradient tensor, the clip norm and the post-step weights.  bf16 (500 is not a multiple of 8: the engine pads
-    the feature dimension internally): the bf16 tolerances."""
+    the feature dimension internally): the bf16 tolerances.  The oracle's step runs in float64 (`_float64`); the few rows whose
+    gradient rests on a LeakyReLU input within fp32 rounding of the kink are left out of the comparisons (`_kink_rows`)."""
     B, dims, L, p = 512, (2000, 1000, 500), 64, 0.6
     model, eng, P, Bf = _pair(jam, dims, L, B, mode, seed=31)
     assert model.num_parameters() == 42738887
-    opt = orc.Adam(P.values(), 1e-3)
     X = _synth(B, dims, seed=4)
     torch.manual_seed(77)
     noise = orc.draw_noise(dims, L, B, p)
     P_e, Bf_e = _clone_state(P, Bf)
-    st = orc.train_step(P, Bf, opt, X, None, None, noise, p, 0.6, return_grads=True)
+    P, Bf, X64, noise64 = _float64(P, Bf, X, noise)
+    P0 = {k: v.detach().clone() for k, v in P.items()}
+    opt = orc.Adam(P.values(), 1e-3)
+    st = orc.train_step(P, Bf, opt, X64, None, None, noise64, p, 0.6, return_grads=True)
+    kink = _kink_rows(P0, X64, st['combined'], noise64, p)
+    assert sum(len(r) for k, r in kink.items() if P0[k].dim() == 2) <= 64      # of 14 000 rows
     init_flat = model.flat.clone()
     eng.set_batch([x.cuda() for x in X])
     eng.set_kl_anneal(0.6)
@@ -403,8 +451,10 @@ def test_config4_full_size_step_vs_generalised_oracle(jam, mode):
     for ref in P:
         if orc.is_dead_bias(ref):
             continue
-        assert_mostly_close(_grad(eng, model, ref), st['grads'][ref].numpy(), rtol=0, atol=0, max_bad_frac=1.0,
-                            rel_l2=1e-1 if bf else 2e-3, msg=ref)
+        got, want = _grad(eng, model, ref), st['grads'][ref].numpy()
+        if ref in kink:
+            got, want = _drop_rows(got, kink[ref]), _drop_rows(want, kink[ref])
+        assert_mostly_close(got, want, rtol=0, atol=0, max_bad_frac=1.0, rel_l2=1e-1 if bf else 2e-3, msg=ref)
     if bf:        # the tight check against the oracle with the same operand roundings (runs the optimiser step)
         _bf16_step_vs_emulating_oracle(eng, model, P_e, Bf_e, X, None, noise, p, 0.6, init_flat)
     else:
@@ -419,8 +469,10 @@ def test_config4_full_size_step_vs_generalised_oracle(jam, mode):
         sd = model.state_dict()
         for k, v in P.items():
             if not orc.is_dead_bias(k):
-                assert_mostly_close(sd[k].cpu().numpy(), v.detach().numpy(), rtol=1e-3, atol=2e-5, max_bad_frac=2e-2,
-                                    rel_l2=1e-2 if v.dim() == 1 else 5e-4, msg=k)
+                got, want = sd[k].cpu().numpy(), v.detach().numpy()
+                if k in kink:
+                    got, want = _drop_rows(got, kink[k]), _drop_rows(want, kink[k])
+                assert_mostly_close(got, want, rtol=1e-3, atol=2e-5, max_bad_frac=2e-2, rel_l2=1e-2 if v.dim() == 1 else 5e-4, msg=k)
         for k, v in Bf.items():
             if 'num_batches' not in k:
                 np.testing.assert_allclose(sd[k].cpu().numpy(), v.numpy(), rtol=1e-4, atol=1e-5, err_msg=k)

@@ -418,7 +418,7 @@ def test_two_ranks_over_rccl_when_two_gpus_are_present(tmp_path):
         pytest.skip('one GPU visible: RCCL with more than one rank needs a GPU per rank')
     clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'JAMIE_DIST_BACKEND',
                                                                'JAMIE_SHARE_GPU')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5', '--full'],
                        capture_output=True, text=True, env=clean, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])

@@ -317,7 +317,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     env = dict(os.environ, JAMIE_DIST_BACKEND='gloo', JAMIE_SHARE_GPU='1', MASTER_ADDR='127.0.0.1')
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', '29577', os.path.join(root, 'bench.py'),
-                        '--gpus', '2', '--steps', '6', '--warmup', '2', '--config', 'c1', '--dtype', 'f32'],
+                        '--gpus', '2', '--steps', '6', '--warmup', '2', '--config', 'c1', '--dtype', 'f32', '--full'],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -332,7 +332,8 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     # ... and the other way round on request
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', '29576', os.path.join(root, 'bench.py'),
-                        '--gpus', '2', '--steps', '6', '--warmup', '2', '--config', 'c1', '--dtype', 'f32', '--dp-optimizer', 'auto'],
+                        '--gpus', '2', '--steps', '6', '--warmup', '2', '--config', 'c1', '--dtype', 'f32', '--dp-optimizer', 'auto',
+                        '--full'],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
@@ -341,7 +342,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path):
     # bf16 compute at N > 1: the line also carries the same job timed with fp32 gradient messages
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                         '--master-addr', '127.0.0.1', '--master-port', '29578', os.path.join(root, 'bench.py'),
-                        '--gpus', '2', '--steps', '8', '--warmup', '2', '--config', 'c1'],
+                        '--gpus', '2', '--steps', '8', '--warmup', '2', '--config', 'c1', '--full'],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
@@ -364,7 +365,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env = dict(clean, JAMIE_DIST_BACKEND='gloo', JAMIE_SHARE_GPU='1')
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2',
-                        '--config', 'c1', '--dtype', 'f32'], capture_output=True, text=True, env=env, timeout=900)
+                        '--config', 'c1', '--dtype', 'f32', '--full'], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -415,6 +416,42 @@ def test_bench_config5_path_two_ranks_at_reduced_cells(tmp_path):
     assert out['config']['features'] == [5000, 2000] and out['config']['parameters'] == 233477258
     assert 'drawn on the device' in out['config']['generator'] and out['config']['grad_allreduce'] == 'f32'
     assert np.isfinite(out['final_loss']) and out['value'] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline line and none of the sub-records; --steps is the number of timed steps and
+    `value` = B / `ms_per_step`.  --dump-outputs writes the last timed step's losses and the parameters after it as float
+    .npy files (at most 64 MB), and a second run with the same arguments writes the same numbers."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    dumps = []
+    for run in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2',
+                            '--config', 'c1', '--dump-outputs', str(tmp_path / run)], capture_output=True, text=True, env=clean,
+                           timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out['steps'] == 5 and out['warmup'] == 2 and out['dtype'] == 'bf16' and out['unit'] == 'cells/s'
+        assert out['higher_is_better'] is True and out['metric'].startswith('training cells/sec')
+        assert out['value'] == pytest.approx(out['config']['batch_per_gpu'] * 1e3 / out['ms_per_step'], rel=1e-9)
+        assert not {'roofline', 'kernel_event_timing_ms', 'steady_state', 'f32', 'other_configs', 'cpu_baseline'} & set(out)
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ['losses.npy', 'parameters.npy']
+        arrs = {f: np.load(tmp_path / run / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        assert arrs['losses.npy'].shape == (5,) and arrs['losses.npy'][4] == pytest.approx(out['final_loss'], rel=1e-6)
+        # (every parameter and the BatchNorm running means and variances: 2 x (2d + d + d + 2d) per modality)
+        assert arrs['parameters.npy'].size == min(out['config']['parameters'] + 12 * sum(out['config']['features']), 1 << 22)
+        dumps.append(arrs)
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)
 
 
 @pytest.mark.parametrize('mode', ['f32_buckets', 'bf16_overlapped_plan'])

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python $ROOT/bench.py --dtype $DT --steps ${STEPS:-200} --warmup 20 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 500 python $ROOT/bench.py --dtype $DT --steps ${STEPS:-200} --warmup 20 --full > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -5 $OUT/bench.err; exit 1; }
 echo "bench done" > $OUT/progress.txt
 # (the profiled passes run the headline leg only: the fp32 record and the other configurations would mix their launches of the
 #  same kernels into the per-kernel averages)
