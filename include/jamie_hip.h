@@ -462,6 +462,35 @@ int jamie_standardise(const void* X, int is_f64, long long N, int d, long long l
                       float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Stage A distances on the device (jamie_amd/distances.py; reference `compute_distances`, jamie.py:839-890, and unioncom's
+ * geodesic_distances, jamie_amd/utilities.py).  D is one N x N fp32 buffer, row-major with ld = N, used in place by every call
+ * below; X is the column-centred data [N, d] fp32 (jamie_col_stats + jamie_standardise with sd = 1) and G = X X^T comes from
+ * jamie_gemm_f32_cfg (JAMIE_NT, configuration 17) written into D.  Deterministic: no floating-point atomics.
+ * ------------------------------------------------------------------------------------------------ */
+/* floats of `partials` jamie_apsp_finalise needs for N cells */
+long long jamie_dist_workspace(long long N);
+/* out[i] = sum_c X[i, c]^2 (fp32) */
+int jamie_row_sqnorm(const float* X, long long N, int d, float* out, void* stream);
+/* D = G -> sqrt(max(n_i + n_j - 2 G_ij, 0)) (squared = 0) or max(n_i + n_j - 2 G_ij, 0) (squared = 1), diagonal exactly 0, exactly
+ * symmetric (both halves from the upper triangle of G): sklearn `pairwise_distances(metric='euclidean' | 'sqeuclidean')` */
+int jamie_gram_to_distances(float* D, const float* sqnorm, long long N, int squared, void* stream);
+/* idx[i, 0] = i, idx[i, 1 .. K) = the K - 1 smallest off-diagonal entries of row i of D, ascending (ties: lower column first); radix
+ * select on the fp32 bits (D >= 0), survivors sorted.  1 <= K <= min(N, 1024): sklearn
+ * `NearestNeighbors(n_neighbors=K).fit(X).kneighbors_graph(X)` (X given explicitly, so the cell is its own first neighbour) */
+int jamie_knn_topk(const float* D, long long N, int K, int32_t* idx, void* stream);
+/* w[i, s] = sqrt(sum_c (X[i, c] - X[idx[i, s], c])^2) in fp32: the kNN graph's edge weights by direct difference */
+int jamie_knn_weights(const float* X, long long N, int d, const int32_t* idx, int K, float* w, void* stream);
+/* D = +inf, diagonal 0, then every edge (i, idx[i, s]) with s < k (of the K columns of idx / w) to D_ij and D_ji, the smaller weight
+ * kept: the graph csgraph `shortest_path(kneighbors_graph, directed=False)` walks */
+int jamie_knn_graph_init(float* D, long long N, const int32_t* idx, const float* w, int K, int k, void* stream);
+/* all-pairs shortest paths in place, blocked Floyd-Warshall on 128 x 128 blocks (rows / columns past N act as +inf padding):
+ * csgraph `shortest_path(method='D', directed=False)` */
+int jamie_apsp_fw(float* D, long long N, void* stream);
+/* D = min(D, D^T); maxv[0] = the largest finite entry (0 if none); every +inf -> 2 maxv[0] (utilities.geodesic_distances' last
+ * step).  `partials`: n_partials >= jamie_dist_workspace(N) floats */
+int jamie_apsp_finalise(float* D, long long N, float* partials, long long n_partials, float* maxv, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

@@ -199,6 +199,14 @@ EXPORTS = {
     'jamie_pd_step': (C.c_int, [C.POINTER(PdState), C.c_int, C.c_void_p]),
     'jamie_pd_alpha': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
                                  C.c_void_p]),
+    'jamie_dist_workspace': (C.c_longlong, [C.c_longlong]),
+    'jamie_row_sqnorm': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_gram_to_distances': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    'jamie_knn_topk': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_knn_weights': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_knn_graph_init': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'jamie_apsp_fw': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_apsp_finalise': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -659,6 +667,39 @@ def standardise_columns(X):
     _call('jamie_col_stats', ptr(X), f64, N, d, d, ptr(part), R, ptr(mean), ptr(sd), _stream())
     _call('jamie_standardise', ptr(X), f64, N, d, d, ptr(mean), ptr(sd), ptr(out), _stream())
     return out, mean, sd
+
+
+# ---- stage A distances (jamie_amd/distances.py; include/jamie_hip.h "Stage A distances on the device") ----
+def dist_workspace(N):
+    return int(load().jamie_dist_workspace(int(N)))
+
+
+def row_sqnorm(X, out):
+    _call('jamie_row_sqnorm', ptr(X), X.shape[0], X.shape[1], ptr(out), _stream())
+
+
+def gram_to_distances(D, sqn, squared=False):
+    _call('jamie_gram_to_distances', ptr(D), ptr(sqn), D.shape[0], int(squared), _stream())
+
+
+def knn_topk(D, K, idx):
+    _call('jamie_knn_topk', ptr(D), D.shape[0], int(K), ptr(idx), _stream())
+
+
+def knn_weights(X, idx, w):
+    _call('jamie_knn_weights', ptr(X), X.shape[0], X.shape[1], ptr(idx), idx.shape[1], ptr(w), _stream())
+
+
+def knn_graph_init(D, idx, w, k):
+    _call('jamie_knn_graph_init', ptr(D), D.shape[0], ptr(idx), ptr(w), idx.shape[1], int(k), _stream())
+
+
+def apsp_fw(D):
+    _call('jamie_apsp_fw', ptr(D), D.shape[0], _stream())
+
+
+def apsp_finalise(D, partials, maxv):
+    _call('jamie_apsp_finalise', ptr(D), D.shape[0], ptr(partials), partials.numel(), ptr(maxv), _stream())
 
 
 class SqRanges:

@@ -26,6 +26,8 @@ _DISTANCE_MODES = [
     'cosine', 'dice', 'hamming', 'jaccard', 'kulsinski', 'mahalanobis', 'matching', 'minkowski',
     'rogerstanimoto', 'russellrao', 'seuclidean', 'sokalmichener', 'sokalsneath', 'sqeuclidean', 'yule',
     'wminkowski', 'nan_euclidean', 'haversine', 'geodesic', 'spearman', 'pearson']
+# the modes of distances='device' (jamie_amd/distances.py)
+_DEVICE_DISTANCE_MODES = ('geodesic', 'euclidean', 'l2', 'sqeuclidean')
 
 
 def init_random_seed(manual_seed):
@@ -63,6 +65,10 @@ class JAMIE:
                    collectives: every rank must call them
       grad_comm_dtype 'auto' (default: the compute dtype), 'f32' or 'bf16': precision of the gradient all-reduce
                    messages when distributed (bf16 halves the 4 P bytes exchanged per step)
+      distances    'host' (default): stage A (`compute_distances`) on the host in float64 with scipy / sklearn, as the reference;
+                   'device': on the MI355X (jamie_amd/distances.py) in fp32 for distance_mode 'geodesic', 'euclidean', 'l2' and
+                   'sqeuclidean' (any other mode raises ValueError): `self.dist` then holds float32 device tensors that go
+                   straight into Prime_Dual, so no N x N matrix crosses PCIe
     """
 
     def __init__(self, match_result=None, PF_Ratio=None, corr_method='unioncom', dist_method='euclidean',
@@ -71,7 +77,7 @@ class JAMIE:
                  min_epochs=2500, min_increment=1e-8, max_steps_without_increment=500, debug=False,
                  log_debug=100, record_loss=True, enable_memory_logging=False, device='cuda',
                  sampler='auto', distributed=False, compute_dtype='f32', grad_comm_dtype='auto', dp_optimizer='replicated',
-                 preprocess='host', checkpoint_path=None, checkpoint_every=0, **kwargs):
+                 preprocess='host', checkpoint_path=None, checkpoint_every=0, distances='host', **kwargs):
         self.match_result = match_result
         self.PF_Ratio = PF_Ratio
         self.corr_method = corr_method
@@ -104,6 +110,9 @@ class JAMIE:
         if preprocess not in ('host', 'device'):
             raise ValueError("preprocess must be 'host' (numpy fp64, the reference's arithmetic) or 'device'")
         self.preprocess = preprocess
+        if distances not in ('host', 'device'):
+            raise ValueError("distances must be 'host' (scipy / sklearn in float64, the reference's arithmetic) or 'device'")
+        self.distances = distances
         # training checkpoints (the reference only pickles the finished model, jamie.py:967-972):
         # every `checkpoint_every` epochs the full training state goes to `checkpoint_path`;
         # fit_transform(..., resume_from=path) continues from it and ends bit-identical to an uninterrupted run
@@ -124,6 +133,9 @@ class JAMIE:
             setattr(self, k, kwargs.pop(k, v))
         if kwargs:
             raise TypeError(f'unexpected keyword arguments: {sorted(kwargs)}')
+        if self.distances == 'device' and self.distance_mode not in _DEVICE_DISTANCE_MODES:
+            raise ValueError(f"distances='device' supports distance_mode {', '.join(map(repr, _DEVICE_DISTANCE_MODES))}; "
+                             f'got {self.distance_mode!r}')
         self.model = None
         self.engine = None
         self.loss_history = {}
@@ -176,16 +188,30 @@ class JAMIE:
 
     # ---- stages A / B (reference jamie.py:224-249, 314-414, 839-890) ----
     def compute_distances(self, save_dist=True):
-        """Cell x cell distance matrix of every modality (host numpy / scipy / sklearn, as in the reference)."""
+        """Cell x cell distance matrix of every modality (host numpy / scipy / sklearn, as in the reference; with
+        distances='device' float32 device tensors from jamie_amd/distances.py)."""
         from .utilities import distance_matrix
         if save_dist:
             self.dist = []
         print('Shape of Raw data')
         for i in range(self.dataset_num):
             print('Dataset {}:'.format(i), np.shape(self.dataset[i]))
-        self.distance_function = lambda df: distance_matrix(df, self.distance_mode, self.kmax)   # noqa: E731
+        if self.distances == 'device':
+            self.distance_function = self._device_distance_function()
+        else:
+            self.distance_function = lambda df: distance_matrix(df, self.distance_mode, self.kmax)   # noqa: E731
         if save_dist:
             self.dist = [self.distance_function(d) for d in self.dataset]
+
+    def _device_distance_function(self):
+        from . import distances as jdist
+        mode = self.distance_mode
+        if mode not in _DEVICE_DISTANCE_MODES:
+            raise ValueError(f"distances='device' supports distance_mode {', '.join(map(repr, _DEVICE_DISTANCE_MODES))}; "
+                             f'got {mode!r}')
+        if mode == 'geodesic':
+            return lambda df: jdist.geodesic(df, self.kmax, device=self.device)            # noqa: E731
+        return lambda df: jdist.euclidean(df, squared=mode == 'sqeuclidean', device=self.device)   # noqa: E731
 
     def Prime_Dual(self, dist, dx=None, dy=None, verbose=True):
         """reference jamie.py:314-414, on the MI355X (jamie_amd/correspondence.py); returns F as numpy float32."""
