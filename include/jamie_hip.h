@@ -103,7 +103,7 @@ int jamie_panel_width(void);
 
 /* One launch computing up to JAMIE_MAX_GEMM_GROUP independent problems (the modalities of one layer; dX and dW together). */
 int jamie_gemm_f32(const jamie_gemm_problem* problems /*host*/, int count, int layout, void* stream);
-/* Same with an explicit tile configuration (tuning / benchmarks); cfg < 0 = choose by shape.  Configurations 0-19 run on the fp32
+/* Same with an explicit tile configuration (tuning / benchmarks); cfg < 0 = choose by shape.  Configurations 0-18 run on the fp32
  * matrix pipe (v_mfma_f32_32x32x2_f32).  Configurations 20 (128 x 128 tiles) and 21 (256 x 128) run the SAME fp32 problem on the bf16 matrix pipe: every fp32 element is cut
  * into three bf16 pieces (x = hi + mid + lo, exact) and a product is six v_mfma_f32_32x32x16_bf16 into an fp32 accumulator -- fp32
  * inputs, fp32 outputs, error at the level of an fp32 product's own rounding (dropped terms <= 2^-21, typically 2^-24 of |a||b|); non-finite inputs
@@ -299,11 +299,6 @@ typedef struct {
     void* dec0_WT_bf16[4];
     int g1_panel, da2_panel;    /* 1: g1[i] / da2[i] are written in panels of JAMIE_PANEL columns (see jamie_gemm_problem.c_panel):
                                  * what the BatchNorm launches that consume them read when their `panel` is set */
-    /* optional (all modalities or none; L <= 64, d[i] a multiple of 8): jamie_latent_m_fwd computes the heads' product itself --
-     * mu | logvar_i = heads_a_bf16[i] [B, d[i]] (bf16: the encoder's output as its BatchNorm launch stored it) x
-     * heads_W_bf16[i] [2L, d[i]]^T (bf16 copy of fc_mu | fc_var, model.py:180,185), fp32 accumulation, + head_bias -- instead of
-     * summing the split-K slabs `ml` of a heads GEMM launch (ml / ml_nslab are ignored then; d[i] must be set) */
-    const void* heads_a_bf16[4]; const void* heads_W_bf16[4];
 } jamie_latent_m;
 /* What a riding sampler draws: idx[B] = jamie_sample_indices(B, N, offset, replace, {seed, step + step_add}, rng_stream)
  * (np.random.choice of jamie/jamie.py:556).  step_add = 1 in a launch that runs before the norm kernel has advanced the step. */

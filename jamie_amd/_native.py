@@ -105,7 +105,7 @@ class LatentM(C.Structure):
                 ('dml_bf16', C.c_void_p * 4), ('dmlT_bf16', C.c_void_p * 4),
                 ('dbias_head', C.c_void_p * 4), ('colpart', C.c_void_p), ('accumulate', C.c_int), ('ticket', C.c_void_p),
                 ('defer_final', C.c_int), ('head_W', C.c_void_p * 4), ('da2', C.c_void_p * 4), ('dec0_WT_bf16', C.c_void_p * 4),
-                ('g1_panel', C.c_int), ('da2_panel', C.c_int), ('heads_a_bf16', C.c_void_p * 4), ('heads_W_bf16', C.c_void_p * 4)]
+                ('g1_panel', C.c_int), ('da2_panel', C.c_int)]
 
 
 class SampleArgs(C.Structure):

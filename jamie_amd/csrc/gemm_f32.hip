@@ -1142,11 +1142,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_f32_dma_kernel(GemmGroup g)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// `solo_lds` > 0: that many bytes of dynamic LDS on top of the kernel's own, so that only ONE workgroup fits a CU (configuration
-// 19: the forward launches that run beside the optimiser stream leave half of each CU's wave slots to clip + Adam -- one workgroup
-// alone on a CU keeps 0.86 of the pair's MFMA rate, profiles/r04_stamps_f32_launches_after.log)
 template <int BM, int BN, int BK, int WM, int WN, bool A_KC, bool B_KC, bool MID = false, int X3 = 0>
-static int launch_cfg(const jamie_gemm_problem* pr, int count, hipStream_t st, int solo_lds = 0) {
+static int launch_cfg(const jamie_gemm_problem* pr, int count, hipStream_t st) {
     GemmGroup g;
     memset(&g, 0, sizeof(g));
     g.count = count;
@@ -1202,18 +1199,9 @@ static int launch_cfg(const jamie_gemm_problem* pr, int count, hipStream_t st, i
         else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BK, WM, WN, A_KC, B_KC, 2, 0, false, X3>), dim3(tiles), dim3(WM * WN * 64), 0, st, g);
         return jamie_launch_status("jamie_gemm_f32");
     }
-    if (fast && big && !tails) {
-        auto kern = gemm_f32_kernel<BM, BN, BK, WM, WN, A_KC, B_KC, 2, 1, MID>;
-        if (solo_lds > 0) {
-            static bool raised = false;          // (once per process: the dynamic-LDS ceiling of this instantiation)
-            if (!raised) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, solo_lds);
-                if (e != hipSuccess) return jamie_fail((int)e, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed [%lld %lld]", "jamie_gemm_f32", solo_lds, 0);
-                raised = true;
-            }
-        }
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(WM * WN * 64), solo_lds > 0 ? solo_lds : 0, st, g);
-    } else if (fast && !tails)
+    if (fast && big && !tails)
+        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BK, WM, WN, A_KC, B_KC, 2, 1, MID>), dim3(tiles), dim3(WM * WN * 64), 0, st, g);
+    else if (fast && !tails)
         hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, BK, WM, WN, A_KC, B_KC, 2, 0, MID>), dim3(tiles),
                            dim3(WM * WN * 64), 0, st, g);
     else if (fast)
@@ -1304,8 +1292,6 @@ static int launch_layout(const jamie_gemm_problem* pr, int count, int cfg, hipSt
         case 16: return launch_cfg<128, 256, 32, 4, 4, A_KC, B_KC>(pr, count, st);    // 16 waves of 32x64
         case 17: return launch_cfg<128, 128, 32, 4, 4, A_KC, B_KC, true>(pr, count, st);   // 12 with the barrier in mid k-step
         case 18: return launch_cfg<64, 64, 32, 2, 2, A_KC, B_KC, true>(pr, count, st);      // 1 likewise
-        // 17 with 56 KB of unused dynamic LDS: one workgroup per CU (64 + 56 KB each of 160), for launches beside the optimiser stream
-        case 19: return launch_cfg<128, 128, 32, 4, 4, A_KC, B_KC, true>(pr, count, st, 56 * 1024);
         // the products on the bf16 matrix pipe, every fp32 element as three bf16 pieces (see the kernel): four waves of 64 x 64
         case 20: return launch_cfg<128, 128, 32, 2, 2, A_KC, B_KC, false, 1>(pr, count, st);
         case 21: return launch_cfg<256, 128, 32, 2, 2, A_KC, B_KC, false, 1>(pr, count, st);      // ... four waves of 128 x 64, two LDS stages

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_bf16_kernel(const unsigned sh
 // 610 -> 598 us: r03_ab_adam_ldnt.log; it is dead once read); the master weights non-temporal cost the kernel 9 us.  Bit 2: the fp32 gradient (fp32 compute mode, fp32 messages) non-temporal as well:
 // config 2 in fp32 1506 -> 1495 us per step, config 5's dimensions 7287 -> 7243 (r03_ab_adam_g32_nt.log): LD_NT = 6.
 // The bf16 weight copy non-temporal or not: no difference once the moments' stores are (W16_NT stays 1).  Starting the streams
-// at the second layer so that the first layer's bf16 weights are written last (state[2]): +5 us, rejected
+// at the second layer so that the first layer's bf16 weights are written last: +5 us, rejected
 // (r03_ab_adam_rotate_rejected.log).
 // (The A/B builds behind these measurements -- -DJAMIE_ADAM_{ST,LD,W16}_NT -- are gone; the adopted policies are written out below.)
 template <int U, int T, bool RIDE>
@@ -108,18 +108,12 @@ __global__ __launch_bounds__(T) void clip_adam_kernel(float* __restrict__ p, con
     float4* v4 = reinterpret_cast<float4*>(v);
     const long long nwg = RIDE ? n_stream : gridDim.x;          // streaming workgroups
     // plain loads/stores: non-temporal variants measured 2 % slower here (tools/bench_adam.py: 4.83 vs 4.75 TB/s)
-    // state[2] (optional, float4 units, < n / 4): the stream STARTS there and wraps around, so that the range in front of it -- the
-    // first layer's parameters when the caller passes the offset of the second layer -- is updated LAST and its bf16 weight copy is
-    // the freshest thing in the caches when the next step's first product reads it
-    const long long rot4 = state[2] > 0 && state[2] < n4 ? state[2] : 0;
     float4 pp[U], mm[U], vv[U], gg[U];
     auto load_batch = [&](long long i0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            long long i = i0 + u * T;
+            const long long i = i0 + u * T;
             if (i < n4) {
-                i += rot4;
-                if (i >= n4) i -= n4;
                 // the moments are read once per step: non-temporal loads (in the step -2..-4 us; the master weights and the
                 // stores of all three measured no better streamed)
                 pp[u] = p4[i];
@@ -178,10 +172,8 @@ __global__ __launch_bounds__(T) void clip_adam_kernel(float* __restrict__ p, con
     for (; i0 < n4;) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            long long i = i0 + u * T;
+            const long long i = i0 + u * T;
             if (i >= n4) continue;
-            i += rot4;
-            if (i >= n4) i -= n4;
             upd(pp[u].x, gg[u].x, mm[u].x, vv[u].x);
             upd(pp[u].y, gg[u].y, mm[u].y, vv[u].y);
             upd(pp[u].z, gg[u].z, mm[u].z, vv[u].z);

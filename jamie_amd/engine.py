@@ -30,10 +30,8 @@ TUNING = {
     'f32_dw_cfg': None, 'f32_dx_cfg': None,      # fp32 tile configurations of the dW / dX launches
     'f32_dw_small_cfg': None,     # ... of the skinny layers' dW launch (decoder layer 0, heads)
     'f32_rows_cfg': None,         # ... of the planned forward / dX launches (the planner's K slices stay)
-    'prefetch': 1,                # BatchNorm prefetch riders: 0 off, 1 the next product's weights, 2 + saved activations
-    'prefetch_f32': '0',          # ... in fp32 mode: '0' off (default: +38 us there), '1' on, 'bwd' backward only
+    'prefetch': 1,                # bf16 mode, BatchNorm prefetch riders: 0 off, 1 the next product's weights
     'stagger': True,              # flat optimiser buffers start 4 KB apart
-    'adam_rotate': False,         # clip + Adam walks from the second layer's region (+5 us: off)
     'f32_dx_plan': True, 'f32_fused_norm': True,
     'f32_x3': True,               # fp32 mode: the large products on the bf16 matrix pipe, every fp32 element cut into three bf16 pieces
                                   # (gemm_f32.hip configuration 20: fp32-level error, 1313 -> 1059 us per step at config 2); False: the
@@ -45,17 +43,9 @@ TUNING = {
                                   # OFF until an N > 1 A/B shows a gain: it adds a launch to the tail of the backward pass and turns
                                   # the merged rep + enc0 message into three all-reduces (~28 us of host enqueue each); bench.py
                                   # --tune split_last_dw=True is the A/B for the first multi-GPU box
-    'fused_heads': False,         # bf16 mode, fused latent kernels, L <= 64: the heads' product mu | logvar = a2 W_h^T inside the latent forward
-                                  # launch (every workgroup multiplies its 32 cells' rows by the whole 2L x d weight) instead of a GEMM launch
-                                  # + 8 split-K slabs.  Built, bit-checked (tests/test_hip_configs.py) and measured SLOWER in round 5: +10.4 us
-                                  # per step (profiles/r05_ab_fused_heads_rejected.log) -- a workgroup has to pull the whole weight (0.4 MB)
-                                  # and its cells' rows (0.2 MB) through ONE CU's 55-66 GB/s: ~10 us, more than the split-K launch it replaces
     'mse_colpart': True,          # the decoder's output-bias gradient from jamie_mse_cast's per-tile column sums (no fp32 d x_hat in bf16 mode)
     'bn_panel': True,             # bf16 mode: the fp32 pre-activations / upstream gradients travel GEMM -> BatchNorm (-> BatchNorm backward)
                                   # in panels of 16 columns (jamie_hip.h: JAMIE_PANEL): a BatchNorm strip is whole contiguous blocks per slab
-    'f32_pipe_solo': 'enc0,enc1',  # fp32, pipelined optimiser: the forward launches of these layers run beside clip + Adam on the optimiser
-                                  # stream and take tile configuration 19 (= 17 at ONE workgroup per CU: half of each CU's wave slots
-                                  # stay free for the streaming kernel); '' = off
     'f32_dw_group': 4,            # fp32, no gradient exchange: the large layers' dW products wait and go out `n` layers per launch
                                   # (4 layers = 2560 tiles of 128 x 128 = 5.0 rounds of 512 slots; one layer = 1.25 rounds); 1: off
 }
@@ -146,7 +136,6 @@ F32_CFG_DW = 17             # fp32 dW (TN, K = batch) of the large layers when t
                             # exchange): the mid-barrier 128x128 tile (round 2's sweep had 64x64, configuration 1; with round 4's loop
                             # config 5's dimensions run 6.86 against 6.97 ms per step, config 2 the same: r04_f32_dp_dw_tile.log)
 F32_CFG_DW_FUSED = 17       # ... 128x128x32 on 16 waves when the launch also writes its tiles' sums of squares (fused clip norm)
-F32_CFG_SOLO = 19           # 17 with 56 KB of unused dynamic LDS: one workgroup per CU (forward launches beside the optimiser stream)
 F32_CFG_X3 = 21             # 256x128x32 on four waves of 128x64, the products as six bf16 MFMAs on three-piece cuts (TUNING['f32_x3']): one
                             # workgroup per CU (144 KB of LDS), ~1.9 us per k-step of twice the work (fp32 pipe, 128x128: 2.05).  20 = the same
                             # on 128x128 tiles (1.0 us per k-step, three LDS stages): 1066 against 993 us per step at config 2
@@ -327,8 +316,6 @@ class TrainEngine:
         self.norm_partials = torch.zeros(self.n_norm, **f32)
         # rng/state: [seed, step, 0, 0]
         self.state = torch.tensor([seed, 0, 0, 0], dtype=torch.int64, device=self.dev)
-        if self.bf16 and TUNING['adam_rotate']:        # (A/B: measured +5 us per step, off)
-            self.set_adam_start(True)
         hyper = torch.zeros(16)
         hyper[H_REC], hyper[H_ALIGN], hyper[H_F] = (self.loss_weights[1], self.loss_weights[2] * ALIGN_WEIGHT,
                                                      self.loss_weights[3])
@@ -578,14 +565,6 @@ class TrainEngine:
             if self._wT_pending:
                 nv.current_stream().wait_event(self._ev_wT)
         self._both(fn)
-
-    def set_adam_start(self, on=True):
-        """clip + Adam walks the flat buffers from the start of the SECOND layer and wraps around (state[2], float4 units): the
-        first layer's parameters are then updated last and its bf16 weights are the freshest lines in the caches when the next
-        step's first product starts (the one forward launch no BatchNorm launch can prefetch for).  Every element sees the
-        same update; only the order of the streams changes."""
-        lo = self.m.layout.regions['enc1'][0] if on else 0
-        self.state[2] = (lo // 4) if lo % 4 == 0 else 0
 
     def enable_pipeline(self, priority=0):
         """Run clip + Adam (and the bf16 weight transposes) on a side stream; `flush()` before anything other than
@@ -858,35 +837,26 @@ class TrainEngine:
             noise[kind][i][j] = m
         return m
 
-    def _prefetch(self, *items):
-        """Ranges for the BatchNorm launches' prefetch rider (jamie_bn_act_fwd_pf / _bwd_pf): what the NEXT launches stream from
-        HBM-cold memory, read into the Infinity Cache by 64 extra workgroups of a launch that has bandwidth to spare.
-        Items: 'W:<layer>' = that layer's weights, both modalities (one contiguous range of the bf16 copy); '<key>' = a workspace
-        tensor of every modality (saved activations the dW products read, the pre-activations the next BatchNorm backward reads).
+    def _prefetch(self, *layers):
+        """Ranges for the BatchNorm launches' prefetch rider (jamie_bn_act_fwd_pf / _bwd_pf): the weights of `layers`, both
+        modalities (one contiguous range of the bf16 copy each), which the NEXT launches stream from HBM-cold memory, read into the
+        Infinity Cache by 64 extra workgroups of a launch that has bandwidth to spare.
         Measured (one box, interleaved, profiles/r03_ab_prefetch.log): bf16 622.2 -> 615.9 us per step with the weights alone (the
         forward launches 27.6 -> 24.6 us each; 64 rider workgroups: 16 / 32 stretch the BatchNorm launch, 695 / 641 us; 128 / 256
         and more loads in flight: no better); fp32 1512 -> 1551 us (those products are bound by the matrix pipe, not by their first
         touch of the weights, and the riders delay the BatchNorm launch): bf16 mode only.  The saved activations on top of the
-        weights (JAMIE_PREFETCH=2): 631.9 against 628.3 us with the weights alone (632.6 without): the extra ranges stretch the
-        BatchNorm launches by what the next launches gain -- the default (1) prefetches the weights only.  JAMIE_PREFETCH=0: off."""
-        mode = str(TUNING['prefetch'])
-        f32_mode = str(TUNING['prefetch_f32'])
-        if mode == '0' or self.pipeline or (not self.bf16 and f32_mode == '0'):
+        weights: 631.9 against 628.3 us with the weights alone (632.6 without): the extra ranges stretch the BatchNorm launches by
+        what the next launches gain.  TUNING['prefetch'] = 0: off."""
+        if str(TUNING['prefetch']) == '0' or self.pipeline or not self.bf16:
             return None
+        if self._zs is not None:
+            return None           # (sharded optimiser: those weights are ARRIVING by all-gather; a rider would read what RCCL writes)
         out = []
-        for it in items:
-            if it.startswith('W:') and self._zs is not None:
-                continue          # (sharded optimiser: those weights are ARRIVING by all-gather; a rider would read what RCCL writes)
-            if it.startswith('W:'):
-                lo, hi = self.m.layout.regions[it[2:]]
-                lo = (lo + 7) // 8 * 8                   # (16-byte aligned in the bf16 copy)
-                out.append((self.wbf_flat if self.bf16 else self.m.flat)[lo:hi])
-            elif mode != '1':
-                for w in self.ws:
-                    t = w.get(it)
-                    if t is not None and t.numel() * t.element_size() >= (1 << 20):
-                        out.append(t[0] if t.dim() == 3 else t)
-        return out[:8] or None
+        for layer in layers:
+            lo, hi = self.m.layout.regions[layer]
+            lo = (lo + 7) // 8 * 8                   # (16-byte aligned in the bf16 copy)
+            out.append(self.wbf_flat[lo:hi])
+        return out or None
 
     def _bn_fwd(self, layer, h_key, out_key, stream_base, noise, kind, j, prefetch=()):
         probs = []
@@ -905,8 +875,6 @@ class TrainEngine:
                 pr.out, pr.out_bf16 = None, nv.ptr(w[out_key + '_bf'])
                 pr.outT_bf16 = nv.ptr(w[out_key + '_T']) if out_key in self.need_T else None
             probs.append(pr)
-        if not self.bf16 and str(TUNING['prefetch_f32']) == 'bwd':
-            prefetch = ()
         nv.bn_act_fwd(probs, self.p_drop, self.state, BN_MOMENTUM, BN_EPS, LRELU_SLOPE, self._prefetch(*prefetch))
 
     def _bn_bwd(self, layer, da_key, h_key, lin, stream_base, noise, kind, j, colsums=None, prefetch=()):
@@ -935,7 +903,7 @@ class TrainEngine:
         round 3: +38 / +120 us per step, profiles/r03_ab_fused_bn_rejected.log; it lives in the experiments build.)"""
         self._fwd_gemm(a_key, lin, h_key, sk_key)
         self._bn_fwd(layer, h_key, out_key, stream_base, noise, kind, j,
-                     prefetch={'enc0': ('W:enc1',), 'dec1': ('W:dec2', 'x')}.get(lin, ()))      # (x: the MSE launch reads it)
+                     prefetch={'enc0': ('enc1',), 'dec1': ('dec2',)}.get(lin, ()))
         self._cast(out_key)
 
     def _fwd_gemm(self, a_key, lin, out_key, sk_key, with_bias=True):
@@ -953,8 +921,6 @@ class TrainEngine:
                                          c_panel=self._paneled(out_key, self.gcfg.get(sk_key, -1))))
         cfg = self.gcfg.get(sk_key, -1)
         fcfg = self.fcfg.get(sk_key, -1)
-        if (not self.bf16 and self.pipeline and fcfg == F32_CFG_ROWS and lin in str(TUNING['f32_pipe_solo']).split(',')):      # (not 20: one per CU as it is)
-            fcfg = F32_CFG_SOLO           # (same tile, same K slices, same sums: one workgroup per CU while clip + Adam streams beside it)
         self._wait_params(lin)
         # 'enc_gemm': every large forward launch; 'enc0_gemm': the encoder's first Linear alone (model.py:151, d -> 2d, both
         # modalities: the matmul north_star's roofline target names; bench.py's roofline.encoder_gemm)
@@ -1155,8 +1121,6 @@ class TrainEngine:
                 d.head_W[i], d.da2[i] = nv.ptr(self.m.p[f'm{i}.head.W']), nv.ptr(w['da2'])
                 d.da2_panel = int(self._paneled('da2'))
             if self.bf16:
-                if getattr(self, '_heads_in_latent', False):
-                    d.heads_a_bf16[i], d.heads_W_bf16[i] = nv.ptr(w['a2_bf']), nv.ptr(self.wbf[f'm{i}.head.W'])
                 d.dml_bf16[i] = nv.ptr(w['dml_bf'])
                 d.dmlT_bf16[i] = nv.ptr(w['dml_T']) if 'dml' in self.need_T else None
                 d.comb_bf16[i] = nv.ptr(w['comb_bf'])
@@ -1331,15 +1295,13 @@ class TrainEngine:
         self._fwd_block('x', 'enc0', 'h1', 'enc0', 'bn0', 'a1', 10, noise, 'enc_masks', 0)
         self._fwd_block('a1', 'enc1', 'h2', 'enc1', 'bn1', 'a2', 11, noise, 'enc_masks', 1)
         fused = fused_losses and self._fused_latent(corr, Fblk)
-        self._heads_in_latent = bool(fused and self.bf16 and self.L <= 64 and TUNING['fused_heads'])
-        if not self._heads_in_latent:
-            self._fwd_gemm('a2', 'head', 'ml', 'head', with_bias=False)
+        self._fwd_gemm('a2', 'head', 'ml', 'head', with_bias=False)
         lat = self._latent_desc(corr, Fblk, noise, fused)
         nv.latent_fwd(lat, self.state)
         if not fused:            # (the fused kernel has written g1 = comb W^T + b and the bf16 copies of comb itself)
             self._cast('comb')
             self._fwd_gemm('comb', 'dec0', 'g1', 'dec0')
-        self._bn_fwd('bn2', 'g1', 'e1', 12, noise, 'dec_masks', 0, prefetch=('W:dec1',))
+        self._bn_fwd('bn2', 'g1', 'e1', 12, noise, 'dec_masks', 0, prefetch=('dec1',))
         self._cast('e1')
         self._fwd_block('e1', 'dec1', 'g2', 'dec1', 'bn3', 'e2', 13, noise, 'dec_masks', 1)
         if not fused_losses:                                              # plain x_hat (autograd seam)
@@ -1463,11 +1425,11 @@ class TrainEngine:
         self._region(allreduce, 'dec2')
         self._bn_bwd('bn3', 'de2', 'g2', 'dec1', 13, noise, 'dec_masks', 1,
                      colsums=nv.colsum_problems(cs_items, acc) if ride else None,
-                     prefetch=('W:dec1', 'e1_bf', 'g1'))   # de2[0] <- dg2p   (next: dX / dW of dec1, then BatchNorm backward on g1)
+                     prefetch=('dec1',))   # de2[0] <- dg2p   (next: dX / dW of dec1, then BatchNorm backward on g1)
         self._cast('de2')
         self._bwd_gemms('de2', 'dec1', 'e1', 'de1', 'd_e1', ranges=dr.get('dec1'))
         self._region(allreduce, 'dec1')
-        self._bn_bwd('bn2', 'de1', 'g1', 'dec0', 12, noise, 'dec_masks', 0, prefetch=('h2', 'a2_bf'))   # de1[0] <- dg1p
+        self._bn_bwd('bn2', 'de1', 'g1', 'dec0', 12, noise, 'dec_masks', 0)   # de1[0] <- dg1p
         self._cast('de1')
         # the heads' input gradient comes out of the latent backward launch (fused kernels); the dW products of the two skinny
         # layers (decoder layer 0, heads: K = batch, the longest tiles of their launches) then ride in the next big layer's
@@ -1496,7 +1458,7 @@ class TrainEngine:
             self._region(allreduce, 'head')
         # (fp32, deferred dW: the skinny layers' dW launch -- 0.3 GFLOP, 16 dependent k-steps, 20 us -- on a second stream beside this
         #  BatchNorm backward launch costs 30 us more than it saves: profiles/r04_ab_f32_skinny_dw_side_stream_rejected.log)
-        self._bn_bwd('bn1', 'da2', 'h2', 'enc1', 11, noise, 'enc_masks', 1, prefetch=('W:enc1', 'a1_bf', 'h1', 'x_bf'))   # da2[0] <- dh2p
+        self._bn_bwd('bn1', 'da2', 'h2', 'enc1', 11, noise, 'enc_masks', 1, prefetch=('enc1',))   # da2[0] <- dh2p
         self._cast('da2')
         self._bwd_gemms('da2', 'enc1', 'a1', 'da1', 'd_a1', extra=late_dw, ranges=dr.get('enc1'))
         for ex in late_dw:
