@@ -466,9 +466,11 @@ int jamie_standardise(const void* X, int is_f64, long long N, int d, long long l
 long long jamie_dist_workspace(long long N);
 /* out[i] = sum_c X[i, c]^2 (fp32) */
 int jamie_row_sqnorm(const float* X, long long N, int d, float* out, void* stream);
-/* D = G -> sqrt(max(n_i + n_j - 2 G_ij, 0)) (squared = 0) or max(n_i + n_j - 2 G_ij, 0) (squared = 1), diagonal exactly 0, exactly
- * symmetric (both halves from the upper triangle of G): sklearn `pairwise_distances(metric='euclidean' | 'sqeuclidean')` */
-int jamie_gram_to_distances(float* D, const float* sqnorm, long long N, int squared, void* stream);
+/* D = G -> sqrt(q) (squared = 0) or q (squared = 1), q = max(n_i + n_j - 2 G_ij, 0), diagonal exactly 0, exactly symmetric (both
+ * halves from the upper triangle of G): sklearn `pairwise_distances(metric='euclidean' | 'sqeuclidean')`.  Where cancellation
+ * dominates, q < 2^-10 (n_i + n_j) (near-duplicate cells), q is recomputed as sum_c (X[i, c] - X[j, c])^2 in fp32 from X [N, d],
+ * the rows sqnorm was taken of: |dD| <= 1.35e-6 c max D for a summation-noise factor c ~ 1, exact duplicates exactly 0 */
+int jamie_gram_to_distances(float* D, const float* sqnorm, const float* X, long long N, int d, int squared, void* stream);
 /* idx[i, 0] = i, idx[i, 1 .. K) = the K - 1 smallest off-diagonal entries of row i of D, ascending (ties: lower column first); radix
  * select on the fp32 bits (D >= 0), survivors sorted.  1 <= K <= min(N, 1024): sklearn
  * `NearestNeighbors(n_neighbors=K).fit(X).kneighbors_graph(X)` (X given explicitly, so the cell is its own first neighbour) */

@@ -201,7 +201,7 @@ EXPORTS = {
                                  C.c_void_p]),
     'jamie_dist_workspace': (C.c_longlong, [C.c_longlong]),
     'jamie_row_sqnorm': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
-    'jamie_gram_to_distances': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    'jamie_gram_to_distances': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
     'jamie_knn_topk': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_knn_weights': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_knn_graph_init': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -678,8 +678,9 @@ def row_sqnorm(X, out):
     _call('jamie_row_sqnorm', ptr(X), X.shape[0], X.shape[1], ptr(out), _stream())
 
 
-def gram_to_distances(D, sqn, squared=False):
-    _call('jamie_gram_to_distances', ptr(D), ptr(sqn), D.shape[0], int(squared), _stream())
+def gram_to_distances(D, sqn, X, squared=False):
+    """X: the [N, d] fp32 rows sqn was taken of (near-duplicate pairs are recomputed from them by direct difference)."""
+    _call('jamie_gram_to_distances', ptr(D), ptr(sqn), ptr(X), D.shape[0], X.shape[1], int(squared), _stream())
 
 
 def knn_topk(D, K, idx):

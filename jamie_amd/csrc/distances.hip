@@ -36,12 +36,21 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------------
 // Tile-pair passes over the N x N buffer: workgroup (I, J), I <= J, owns the tiles (I, J) and (J, I) and reads both before it
 // writes either, so the pass runs in place and its output is exactly symmetric.
-//   MODE 0: Gram -> euclidean, D = sqrt(max(n_i + n_j - 2 G_ij, 0)), diagonal exactly 0 (G_ij read from the upper triangle)
-//   MODE 1: Gram -> squared euclidean, same without the sqrt
+//   MODE 0: Gram -> euclidean, D = sqrt(q), q = max(n_i + n_j - 2 G_ij, 0), diagonal exactly 0 (G_ij read from the upper triangle)
+//   MODE 1: Gram -> squared euclidean, D = q
 //   MODE 2: D = min(D, D^T); partial[blk] = largest finite value of the two tiles (0 if none)
+// Modes 0 / 1 recompute q by direct difference, sum_c (x_ic - x_jc)^2 in fp32, where cancellation dominates: q < DIST_TAU (n_i + n_j).
+// n (row_sqnorm_kernel) and G (the MFMA GEMM) round in different orders, so q carries an error of c u (n_i + n_j), u = 2^-24, c ~ 1
+// (a few at d = 2000): on (near-)duplicate cells it swamps q.  A pair that keeps the Gram form has q >= tau s (s = n_i + n_j), so
+// |dD| <= c u s / (2 sqrt(q)) <= c u sqrt(s / tau) / 2; centred data has, for every i, a j with x_i . x_j <= 0, so
+// max D^2 >= max n >= s / 2, and |dD| <= c u / sqrt(2 tau) max D = 1.35e-6 c max D at tau = 2^-10 (the 1e-5 max D contract holds for
+// c <= 7).  Gaussian data recomputes nothing (q ~ s); exact duplicates come out exactly 0.
 // ------------------------------------------------------------------------------------------------
+#define DIST_TAU 0x1p-10f
+
 template <int MODE>
-__global__ __launch_bounds__(256) void tile_pair_kernel(float* D, long long N, const float* __restrict__ sqn, float* partial) {
+__global__ __launch_bounds__(256) void tile_pair_kernel(float* D, long long N, const float* __restrict__ sqn, const float* __restrict__ X,
+                                                        int d, float* partial) {
     const int I = blockIdx.y, J = blockIdx.x;
     const int nt = gridDim.x;
     __shared__ float sA[DIST_PT][DIST_PT + 1], sB[DIST_PT][DIST_PT + 1];
@@ -60,20 +69,41 @@ __global__ __launch_bounds__(256) void tile_pair_kernel(float* D, long long N, c
     }
     __syncthreads();
     float mx = 0.f;
-    for (int r = ty; r < DIST_PT; r += 4) {
+    for (int r = ty; r < DIST_PT; r += 4) {                                // (r, hence i, is uniform in a wave; j = j0 + lane)
         const int c = tx;
         const long long i = i0 + r, j = j0 + c;
-        if (i >= N || j >= N) continue;
-        float v;
+        const bool ok = i < N && j < N;
+        float v = 0.f;
         if (MODE == 2) {
-            v = fminf(sA[r][c], sB[c][r]);                                 // D_ij, D_ji
-            if (v < d_inf()) mx = fmaxf(mx, v);
+            if (ok) {
+                v = fminf(sA[r][c], sB[c][r]);                             // D_ij, D_ji
+                if (v < d_inf()) mx = fmaxf(mx, v);
+            }
         } else {
-            const float g = (I < J || r <= c) ? sA[r][c] : sA[c][r];       // G of the upper triangle
-            float q = fmaxf(sqn[i] + sqn[j] - 2.f * g, 0.f);
-            if (i == j) q = 0.f;
+            float q = 0.f;
+            bool redo = false;
+            if (ok) {
+                const float g = (I < J || r <= c) ? sA[r][c] : sA[c][r];   // G of the upper triangle
+                q = fmaxf(sqn[i] + sqn[j] - 2.f * g, 0.f);
+                redo = i != j && q < DIST_TAU * (sqn[i] + sqn[j]);
+                if (i == j) q = 0.f;
+            }
+            // the wave recomputes its flagged pairs one at a time, 64 lanes over the d columns (fixed order: deterministic)
+            for (unsigned long long m = __ballot(redo); m; m &= m - 1) {
+                const int l = __builtin_ctzll(m);
+                const float* xi = X + i * d;
+                const float* xj = X + (j0 + l) * d;
+                float s = 0.f;
+                for (int cc = tx; cc < d; cc += 64) {
+                    const float t = xi[cc] - xj[cc];
+                    s = fmaf(t, t, s);
+                }
+                s = wave_sum(s);
+                if (tx == l) q = s;
+            }
             v = MODE == 0 ? sqrtf(q) : q;
         }
+        if (!ok) continue;
         D[i * N + j] = v;
         if (I != J) D[j * N + i] = v;
     }
@@ -427,11 +457,11 @@ extern "C" int jamie_row_sqnorm(const float* X, long long N, int d, float* out, 
     return jamie_launch_status("jamie_row_sqnorm");
 }
 
-extern "C" int jamie_gram_to_distances(float* D, const float* sqnorm, long long N, int squared, void* stream) {
-    JAMIE_ARG(D && sqnorm && N > 0 && N <= (1 << 24), "null pointer / 0 < N <= 2^24");
+extern "C" int jamie_gram_to_distances(float* D, const float* sqnorm, const float* X, long long N, int d, int squared, void* stream) {
+    JAMIE_ARG(D && sqnorm && X && N > 0 && N <= (1 << 24) && d > 0, "null pointer / 0 < N <= 2^24 / d > 0");
     const int nt = dist_tiles(N);
-    if (squared) hipLaunchKernelGGL(tile_pair_kernel<1>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, nullptr);
-    else hipLaunchKernelGGL(tile_pair_kernel<0>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, nullptr);
+    if (squared) hipLaunchKernelGGL(tile_pair_kernel<1>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr);
+    else hipLaunchKernelGGL(tile_pair_kernel<0>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr);
     return jamie_launch_status("jamie_gram_to_distances");
 }
 
@@ -478,7 +508,7 @@ extern "C" int jamie_apsp_finalise(float* D, long long N, float* partials, long 
     const int nt = dist_tiles(N);
     JAMIE_ARG(n_partials >= (long long)nt * nt, "n_partials < jamie_dist_workspace(N)");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tile_pair_kernel<2>, dim3(nt, nt), dim3(256), 0, st, D, N, nullptr, partials);
+    hipLaunchKernelGGL(tile_pair_kernel<2>, dim3(nt, nt), dim3(256), 0, st, D, N, nullptr, nullptr, 0, partials);
     hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, st, partials, (long long)nt * nt, maxv);
     const long long blocks = (N * N + 255) / 256;
     hipLaunchKernelGGL(fill_unreachable_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, D, N * N, maxv);

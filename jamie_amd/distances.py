@@ -20,10 +20,13 @@ from . import _native as nv
 
 GRAM_CFG = 17          # gemm_f32.hip: 128 x 128 tiles on the fp32 matrix pipe (exact fp32; not the bf16x3 pieces)
 K_MIN = 5              # growth loop of geodesic_distances: k from 5, +2 per step
+TOPK_MAX = 1024        # largest K of jamie_knn_topk (csrc/distances.hip)
 
 
 def _device_input(X, device='cuda'):
-    """numpy (dense or with .toarray()) or a tensor -> contiguous fp32 / fp64 device tensor [N, d]."""
+    """numpy (dense or with .toarray()) or a tensor -> contiguous fp32 / fp64 device tensor [N, d]; any other dtype (integers)
+    goes to fp64, so that it centres exactly as the same values given as fp64 do.  NaN / inf raise ValueError, as sklearn does
+    on the host path."""
     nv.require_gpu()
     if torch.is_tensor(X):
         t = X.to(device)
@@ -31,9 +34,11 @@ def _device_input(X, device='cuda'):
         X = X.toarray() if hasattr(X, 'toarray') else np.asarray(X)
         t = torch.from_numpy(np.ascontiguousarray(X)).to(device)
     if t.dtype not in (torch.float32, torch.float64):
-        t = t.to(torch.float32)
+        t = t.to(torch.float64)
     if t.dim() != 2:
         raise ValueError(f'distances: X must be 2-D [cells, features], got shape {tuple(t.shape)}')
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('distances: X contains NaN or infinity')
     return t.contiguous()
 
 
@@ -59,7 +64,7 @@ def _euclidean_centred(Xc, squared=False, out=None):
     nv.gemm([nv.gemm_problem(Xc, Xc, D, N, N, d, d, d, N)], nv.NT, GRAM_CFG)           # G = Xc Xc^T
     sqn = torch.empty(N, dtype=torch.float32, device=Xc.device)
     nv.row_sqnorm(Xc, sqn)
-    nv.gram_to_distances(D, sqn, squared)
+    nv.gram_to_distances(D, sqn, Xc, squared)
     return D
 
 
@@ -92,6 +97,8 @@ def knn(X, k, device='cuda'):
     kk = int(min(k, N))
     if kk < 1:
         raise ValueError('knn: k must be >= 1')
+    if kk > TOPK_MAX:
+        raise ValueError(f'knn: k = {kk} neighbours; the device top-K takes at most {TOPK_MAX}')
     D = _euclidean_centred(Xc)
     return _knn_centred(Xc, kk, D)
 
@@ -108,7 +115,8 @@ def _connected(idx_host, k):
 
 def geodesic(X, kmax, return_graph=False, device='cuda'):
     """utilities.geodesic_distances on the device: [N, N] float32 tensor.  `return_graph`: also (k, idx [N, K], w [N, K]) -- the
-    k the growth loop chose (clipped to N) and the top-K lists it took prefixes of, K = k_max(N, kmax)."""
+    k the growth loop chose (clipped to N) and the top-K lists it took prefixes of, K = min(k_max(N, kmax), TOPK_MAX).
+    A growth loop that needs more than TOPK_MAX neighbours raises ValueError, before the graph and Floyd-Warshall passes."""
     Xc = centred(X, device)
     N = Xc.shape[0]
     if N == 1:
@@ -117,14 +125,17 @@ def geodesic(X, kmax, return_graph=False, device='cuda'):
             z = torch.zeros(1, 1, device=Xc.device)
             return D, 1, z.to(torch.int32), z
         return D
-    K = k_max(N, kmax)
+    K = min(k_max(N, kmax), TOPK_MAX)
     D = _euclidean_centred(Xc)
     idx, w = _knn_centred(Xc, K, D)
     idx_host = idx.cpu().numpy()
     # growth loop of geodesic_distances: the graph of k neighbours is the first min(k, N) columns of the top-K lists
     k = K_MIN
-    while not _connected(idx_host, min(k, N)):
-        if k > np.max((kmax, 0.01 * N)):
+    while True:
+        if min(k, N) > K:
+            raise ValueError(f'geodesic: the kNN graph is still disconnected at k = {K} and kmax = {kmax} asks for more '
+                             f'neighbours; the device top-K takes at most {TOPK_MAX} (use the host path)')
+        if _connected(idx_host, min(k, N)) or k > np.max((kmax, 0.01 * N)):
             break
         k += 2
     k = min(k, N)

@@ -143,6 +143,35 @@ def test_gemm_f32_three_bf16_pieces_keep_fp32(nv, layout, x3):
         assert e3 <= 4 * e1 + 1e-7, (layout, m, n, k, sk, e3, e1)
 
 
+@pytest.mark.parametrize('cfg', [17, 20, 21])
+@pytest.mark.parametrize('layout', ['NT', 'NN'])
+def test_gemm_f32_output_beyond_4gib(nv, layout, cfg):
+    """C of 33001 x 33001 fp32 (4.36 GB > 4 GiB; ragged against the 128 / 256 tiles): the generic epilogue (c_bytes = 0) and, at
+    65536 tiles or more, the divided tile decode (inv_tm = 0).  Every element written (C starts as NaN, checked on the device);
+    sampled rows and columns against float64, rows past byte offset 2^32 and the last tile row and column among them."""
+    M = N = 33001
+    K = 64
+    g = torch.Generator().manual_seed(cfg + len(layout))
+    a, b = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g)
+    out = torch.full((M, N), float('nan'), device='cuda')
+    if layout == 'NT':
+        nv.gemm([nv.gemm_problem(dev(a), dev(b.t()), out, M, N, K, K, K, N)], nv.NT, cfg)
+    else:
+        bp = torch.zeros(K, N + 3)                     # ldb a multiple of 4 (the vector-load path)
+        bp[:, :N] = b
+        nv.gemm([nv.gemm_problem(dev(a), dev(bp), out, M, N, K, K, N + 3, N)], nv.NN, cfg)
+    assert bool(torch.isfinite(out).all())
+    edge = (1 << 32) // (4 * N)
+    rows = torch.tensor(sorted({0, 127, 128, edge - 1, edge, edge + 1, 32767, 32768, 32895, 32896, N - 1}
+                               | set(torch.randint(0, M, (8,), generator=g).tolist())))
+    cols = torch.tensor(sorted({0, 127, 128, 32767, 32768, 32895, 32896, N - 1} | set(torch.randint(0, N, (8,), generator=g).tolist())))
+    tol = dict(rtol=1e-5, atol=2e-6 * float(np.sqrt(K)))
+    close(out[rows.cuda()], a[rows].double() @ b.double(), msg=f'{layout} cfg {cfg} rows', **tol)
+    close(out[:, cols.cuda()], a.double() @ b[:, cols].double(), msg=f'{layout} cfg {cfg} columns', **tol)
+    del out
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize('cfg', [1, 12, 17, 18, 20, 21])
 @pytest.mark.parametrize('layout', ['NT', 'NN', 'TN'])
 def test_gemm_f32_rows_that_end_inside_a_float4(nv, layout, cfg):

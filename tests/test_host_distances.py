@@ -109,3 +109,105 @@ def test_distances_keyword_is_validated():
     for mode in ('geodesic', 'euclidean', 'l2', 'sqeuclidean'):
         assert jamie_amd.JAMIE(distances='device', distance_mode=mode).distances == 'device'
     assert jamie_amd.JAMIE().distances == 'host'
+
+
+# ---- duplicates, ties and the Gram form's cancellation (shared with test_hip_distances.py) ----
+TAU = 2.0 ** -10            # csrc/distances.hip DIST_TAU: q < TAU (n_i + n_j) is recomputed by direct difference
+
+
+def duplicate_data(d, seed=0):
+    """A Gaussian background of 600 cells plus the near-duplicates of real single-cell data: exact copies of 20 cells, 6 groups of
+    12 copies with noise sigma = 1e-3 around a background cell, and one group of 45 copies of a cell (46 identical cells, more
+    than kmax = 40).  Rows shuffled, so that the duplicates meet across tiles."""
+    rng = np.random.default_rng(seed + d)
+    B = rng.standard_normal((600, d))
+    exact = B[rng.choice(600, 20, replace=False)]
+    noisy = np.repeat(B[rng.choice(600, 6, replace=False)], 12, axis=0) + 1e-3 * rng.standard_normal((72, d))
+    group = np.repeat(B[rng.integers(600)][None], 45, axis=0)
+    X = np.concatenate([B, exact, noisy, group])
+    return X[rng.permutation(len(X))]
+
+
+def tie_rule_order(D, K):
+    """jamie_knn_topk's order in float64: per row the cell itself, then the other columns ascending by (D, column); first K."""
+    N = len(D)
+    D = np.array(D, np.float64)
+    np.fill_diagonal(D, -1.0)
+    return np.lexsort((np.broadcast_to(np.arange(N), D.shape), D), axis=1)[:, :K]
+
+
+def tie_rule_geodesic(X, kmax, D=None):
+    """utilities.geodesic_distances restated in float64 with jamie_knn_topk's tie rule: the growth loop's graph of k neighbours is
+    the first k columns of tie_rule_order (explicit zero weights are edges, as in kneighbors_graph).  -> (dist, k)."""
+    import scipy.sparse as sp
+    import scipy.sparse.csgraph as csgraph
+    from scipy.spatial.distance import cdist
+    X = np.asarray(X, np.float64)
+    N = len(X)
+    D = cdist(X, X) if D is None else D
+    order = tie_rule_order(D, min(N, max(int(kmax) + 2, int(np.ceil(0.01 * N)) + 2, 5)))
+
+    def graph(k):
+        k = min(k, N)
+        rows, cols = np.repeat(np.arange(N), k), order[:, :k].ravel()
+        return sp.csr_matrix((D[rows, cols], (rows, cols)), shape=(N, N))
+    k = 5
+    while csgraph.connected_components(graph(k), directed=False)[0] != 1:
+        if k > np.max((kmax, 0.01 * N)):
+            break
+        k += 2
+    dist = csgraph.shortest_path(graph(k), method='D', directed=False)
+    fin = dist[np.isfinite(dist)]
+    dist[~np.isfinite(dist)] = 2 * (fin.max() if fin.size else 0.0)
+    return dist, min(k, N)
+
+
+def _gram_form_fp32(X):
+    """Centred fp32 rows and q = n_i + n_j - 2 G_ij in fp32 with the device's two summation orders: n lane by lane (64 strided
+    partial sums, then a tree), G one fp32 matrix product.  -> (Xc, q, n_i + n_j)."""
+    Xc = (X - X.mean(0)).astype(np.float32)
+    N, d = Xc.shape
+    P = np.zeros((N, -(-d // 64) * 64), np.float32)
+    P[:, :d] = Xc
+    n = np.zeros((N, 64), np.float32)
+    for c in range(0, P.shape[1], 64):
+        n = n + P[:, c:c + 64] * P[:, c:c + 64]
+    while n.shape[1] > 1:
+        n = n[:, 0::2] + n[:, 1::2]
+    s = n[:, 0][:, None] + n[:, 0][None, :]
+    return Xc, np.maximum(s - np.float32(2) * (Xc @ Xc.T), 0).astype(np.float32), s
+
+
+@pytest.mark.parametrize('d', [16, 50, 2000])
+def test_recomputing_cancelled_pairs_restores_the_euclidean_contract(d):
+    """The rule of jamie_gram_to_distances restated: on near-duplicate cells the Gram form alone is off by far more than
+    1e-5 max D (and exact duplicates do not come out 0); recomputing the pairs with q < TAU (n_i + n_j) by direct difference
+    brings both back, and on plain Gaussian data it recomputes nothing."""
+    from scipy.spatial.distance import cdist
+    X = duplicate_data(d)
+    want = cdist(X, X)
+    Xc, q, s = _gram_form_fp32(X)
+    np.fill_diagonal(q, 0)
+    err0 = np.abs(np.sqrt(q) - want).max() / want.max()
+    assert err0 > 1e-5, err0                                   # the case the device tests exercise
+    redo = (q < np.float32(TAU) * s) & ~np.eye(len(X), dtype=bool)
+    ii, jj = np.nonzero(redo)
+    q[ii, jj] = ((Xc[ii] - Xc[jj]) ** 2).sum(1, dtype=np.float32)
+    err = np.abs(np.sqrt(q) - want).max() / want.max()
+    assert err <= 1e-5, err
+    assert (np.sqrt(q)[want == 0] == 0).all()
+    assert redo.mean() < 0.01
+    _, qg, sg = _gram_form_fp32(np.random.default_rng(d).standard_normal((700, d)))
+    np.fill_diagonal(qg, np.inf)
+    assert not (qg < np.float32(TAU) * sg).any()
+
+
+@pytest.mark.parametrize('d', [16, 2000])
+def test_tie_rule_geodesic_equals_the_host_path_on_duplicates(d):
+    """What the device's geodesic is held to on duplicate_data: its tie rule picks other identical cells than sklearn does, but
+    identical cells are interchangeable, so the distances are the host path's."""
+    from jamie_amd.utilities import geodesic_distances
+    X = duplicate_data(d)
+    got, _ = tie_rule_geodesic(X, 40)
+    want = geodesic_distances(X, 40)         # (sklearn takes kNN distances in the Gram form: exact duplicates ~1e-7 apart)
+    np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-7 * want.max())
