@@ -488,6 +488,31 @@ int jamie_apsp_fw(float* D, long long N, void* stream);
 int jamie_apsp_finalise(float* D, long long N, float* partials, long long n_partials, float* maxv, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Alignment metrics on the device (jamie_amd/metrics.py; reference `test_closer`, jamie.py:892-915, and `test_LabelTA`,
+ * jamie.py:943-961).  All pairs between two fp32 [N, L] row-major embeddings, reduced on the fly to O(N) numbers: nothing of size
+ * N x N is stored.  q(i, j) = sum_c (X[i, c] - Y[j, c])^2 by direct difference in fp32, accumulated in ascending c -- one
+ * instruction chain for every q, so equal operands give equal bits; exact on integer-valued data.  Deterministic: integer adds
+ * only.  Long pair spaces are split over several launches inside one call.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` for jamie_cross_knn(Nq, Nr, K); for jamie_foscttm_counts on N cells ask with (N, N, 0) */
+long long jamie_metrics_workspace(long long Nq, long long Nr, int K);
+/* Cell i of A is paired with cell i of B.  row_closer[i] = #{ j != i : q(i, j) < q(i, i) }, col_closer[j] = #{ i != j : q(i, j) <
+ * q(j, j) }, int32 [N] each, from one pass over the pair space (strict <; j = i excluded by index): the two sums of the loop of
+ * `test_closer` (`ld < ld[i]` over `d[i][size:]` and over `d[size + i][:size]`), FOSCTTM = (sum row_closer + sum col_closer) /
+ * (2 N^2).  q(i, i) is taken first, by the chain of the pair tiles, into ws (N floats) */
+int jamie_foscttm_counts(const float* A, const float* B, long long N, int L, int32_t* row_closer, int32_t* col_closer, void* ws,
+                         long long ws_bytes, void* stream);
+/* For every row of Q [Nq, L] the K rows of R [Nr, L] nearest to it, ascending by (distance, then lower index of R): idx int32
+ * [Nq, K], dist fp32 [Nq, K] = sqrt(q), 1 <= K <= min(Nr, 64) (anything else returns an error before a launch): sklearn
+ * `NearestNeighbors(n_neighbors=K).fit(R).kneighbors(Q)`.  A workgroup keeps the running lists of its 128 (K <= 16) or 64 queries on
+ * chip while it walks its share of R through LDS; the shares' lists are merged in share order */
+int jamie_cross_knn(const float* Q, long long Nq, const float* R, long long Nr, int L, int K, int32_t* idx, float* dist, void* ws,
+                    long long ws_bytes, void* stream);
+/* pred[q] = the class code most frequent among ref_codes[idx[q, 0 .. K)] (0 <= code < n_classes), the lowest such code on a tie:
+ * sklearn `KNeighborsClassifier(weights='uniform').predict` with the classes in `np.unique` order */
+int jamie_knn_vote(const int32_t* idx, long long Nq, int K, const int32_t* ref_codes, int n_classes, int32_t* pred, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

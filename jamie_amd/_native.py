@@ -207,6 +207,12 @@ EXPORTS = {
     'jamie_knn_graph_init': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'jamie_apsp_fw': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_apsp_finalise': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'jamie_metrics_workspace': (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int]),
+    'jamie_foscttm_counts': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_longlong, C.c_void_p]),
+    'jamie_cross_knn': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_knn_vote': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -701,6 +707,26 @@ def apsp_fw(D):
 
 def apsp_finalise(D, partials, maxv):
     _call('jamie_apsp_finalise', ptr(D), D.shape[0], ptr(partials), partials.numel(), ptr(maxv), _stream())
+
+
+# ---- alignment metrics (jamie_amd/metrics.py; include/jamie_hip.h "Alignment metrics on the device") ----
+def metrics_workspace(Nq, Nr, K):
+    """Bytes of workspace for cross_knn(Nq, Nr, K); for foscttm_counts on N cells: (N, N, 0)."""
+    return int(load().jamie_metrics_workspace(int(Nq), int(Nr), int(K)))
+
+
+def foscttm_counts(A, B, row_closer, col_closer, ws):
+    _call('jamie_foscttm_counts', ptr(A), ptr(B), A.shape[0], A.shape[1], ptr(row_closer), ptr(col_closer), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
+
+
+def cross_knn(Q, R, K, idx, dist, ws):
+    _call('jamie_cross_knn', ptr(Q), Q.shape[0], ptr(R), R.shape[0], Q.shape[1], int(K), ptr(idx), ptr(dist), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
+
+
+def knn_vote(idx, ref_codes, n_classes, pred):
+    _call('jamie_knn_vote', ptr(idx), idx.shape[0], idx.shape[1], ptr(ref_codes), int(n_classes), ptr(pred), _stream())
 
 
 class SqRanges:

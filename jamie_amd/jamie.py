@@ -69,6 +69,9 @@ class JAMIE:
                    'device': on the MI355X (jamie_amd/distances.py) in fp32 for distance_mode 'geodesic', 'euclidean', 'l2' and
                    'sqeuclidean' (any other mode raises ValueError): `self.dist` then holds float32 device tensors that go
                    straight into Prime_Dual, so no N x N matrix crosses PCIe
+      metrics      'host' (default): `test_closer` / `test_LabelTA` on the host with sklearn in float64, as the reference (a
+                   2N x 2N distance matrix: a few thousand cells at most); 'device': on the MI355X (jamie_amd/metrics.py)
+                   in fp32 without any N x N matrix, euclidean only, for whole data sets
     """
 
     def __init__(self, match_result=None, PF_Ratio=None, corr_method='unioncom', dist_method='euclidean',
@@ -77,7 +80,8 @@ class JAMIE:
                  min_epochs=2500, min_increment=1e-8, max_steps_without_increment=500, debug=False,
                  log_debug=100, record_loss=True, enable_memory_logging=False, device='cuda',
                  sampler='auto', distributed=False, compute_dtype='f32', grad_comm_dtype='auto', dp_optimizer='replicated',
-                 preprocess='host', checkpoint_path=None, checkpoint_every=0, distances='host', **kwargs):
+                 preprocess='host', checkpoint_path=None, checkpoint_every=0, distances='host', metrics='host',
+                 **kwargs):
         self.match_result = match_result
         self.PF_Ratio = PF_Ratio
         self.corr_method = corr_method
@@ -113,6 +117,9 @@ class JAMIE:
         if distances not in ('host', 'device'):
             raise ValueError("distances must be 'host' (scipy / sklearn in float64, the reference's arithmetic) or 'device'")
         self.distances = distances
+        if metrics not in ('host', 'device'):
+            raise ValueError("metrics must be 'host' (sklearn in float64, the reference's arithmetic) or 'device'")
+        self.metrics = metrics
         # training checkpoints (the reference only pickles the finished model, jamie.py:967-972):
         # every `checkpoint_every` epochs the full training state goes to `checkpoint_path`;
         # fit_transform(..., resume_from=path) continues from it and ends bit-identical to an uninterrupted run
@@ -682,10 +689,17 @@ class JAMIE:
         self.model = m.to(self.device)
         self.dataset_num = self.model.num_modalities
 
-    # ---- metrics kept for sanity checks (reference jamie.py:892-915) ----
+    # ---- acceptance metrics (reference jamie.py:892-915 and 943-961); metrics='device': jamie_amd/metrics.py ----
     def test_closer(self, integrated_data, distance_metric=None):
         """FOSCTTM: fraction of samples closer than the true match."""
         assert len(integrated_data) == 2, 'Two datasets are supported for FOSCTTM'
+        if self.metrics == 'device':
+            if distance_metric not in (None, 'euclidean'):
+                raise ValueError(f"metrics='device' computes FOSCTTM on euclidean distances only, not {distance_metric!r}")
+            from . import metrics as jmetrics
+            foscttm = jmetrics.foscttm(integrated_data[0], integrated_data[1], device=self.device)
+            print(f'foscttm: {foscttm}')
+            return foscttm
         from sklearn.metrics.pairwise import pairwise_distances
         d = pairwise_distances(np.concatenate(integrated_data, axis=0), metric='euclidean')
         size = integrated_data[0].shape[0]
@@ -698,3 +712,22 @@ class JAMIE:
         foscttm = closer / (2 * size ** 2)
         print(f'foscttm: {foscttm}')
         return foscttm
+
+    def test_LabelTA(self, integrated_data, datatype, k=5):
+        """Label transfer accuracy: a k-nearest-neighbour classifier fitted on integrated_data[1] with datatype[1] predicts the
+        labels of integrated_data[0]; its accuracy against datatype[0]."""
+        if self.metrics == 'device':
+            from . import metrics as jmetrics
+            acc = jmetrics.label_transfer_accuracy(integrated_data[0], datatype[0], integrated_data[1], datatype[1], k=k,
+                                                   device=self.device)
+        else:
+            from sklearn.neighbors import KNeighborsClassifier
+            knn = KNeighborsClassifier(n_neighbors=k)
+            knn.fit(_host_array(integrated_data[1]), np.asarray(datatype[1]))
+            acc = float(np.mean(knn.predict(_host_array(integrated_data[0])) == np.asarray(datatype[0])))
+        print(f'label transfer accuracy: {acc}')
+        return acc
+
+
+def _host_array(x):
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)

@@ -41,6 +41,28 @@ def device_disassembly(obj):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def kernel_metadata(obj):
+    """{kernel symbol: {field: int}} from the code-object notes of host object `obj` (or of `obj` itself if it is a code object):
+    `.private_segment_fixed_size` (scratch bytes per lane), `.group_segment_fixed_size`, `.vgpr_count`, `.sgpr_count`, ..."""
+    readelf = os.path.join(os.path.dirname(OBJDUMP), 'llvm-readelf')
+    tmp = tempfile.mkdtemp(prefix='jamie_isa_')
+    try:
+        local = os.path.join(tmp, os.path.basename(obj))
+        shutil.copy(obj, local)
+        subprocess.run([OBJDUMP, '--offloading', local], check=True, capture_output=True, text=True)
+        dev = [f for f in os.listdir(tmp) if 'amdgcn' in f]
+        target = os.path.join(tmp, dev[0]) if dev else local
+        notes = subprocess.run([readelf, '--notes', target], check=True, capture_output=True, text=True).stdout
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    out = {}
+    for block in re.split(r'\n\s*- (?=\.)', notes):
+        name = re.search(r'^\s*\.name:\s+(\S+)', block, flags=re.M)
+        if name and '.private_segment_fixed_size' in block:
+            out[name.group(1)] = {k: int(v) for k, v in re.findall(r'^\s*\.(\w+):\s+(\d+)\s*$', block, flags=re.M)}
+    return out
+
+
 class Inst:
     __slots__ = ('addr', 'size', 'op', 'args', 'func')
 
