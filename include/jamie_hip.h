@@ -471,6 +471,25 @@ int jamie_row_sqnorm(const float* X, long long N, int d, float* out, void* strea
  * dominates, q < 2^-10 (n_i + n_j) (near-duplicate cells), q is recomputed as sum_c (X[i, c] - X[j, c])^2 in fp32 from X [N, d],
  * the rows sqnorm was taken of: |dD| <= 1.35e-6 c max D for a summation-noise factor c ~ 1, exact duplicates exactly 0 */
 int jamie_gram_to_distances(float* D, const float* sqnorm, const float* X, long long N, int d, int squared, void* stream);
+/* out[i, :] = (X[i, :] - m_i) / |X[i, :] - m_i| as fp32 [N, d], m_i = the mean of row i (centre = 1) or 0 (centre = 0); mean, norm and
+ * quotient in fp64, one rounding at the store.  X is fp32 (is_f64 = 0) or fp64 (1), NOT column-centred.  norm[i] = the norm as fp32,
+ * exactly 0 for a zero row and, with centre = 1, for a constant row (every entry equal); such a row is written as zeros: the rows
+ * sklearn `normalize` leaves alone and scipy's `correlation` / `np.corrcoef` turn into NaN */
+int jamie_row_normalise(const void* X, int is_f64, long long N, int d, int centre, float* out, float* norm, void* stream);
+/* D = G -> scale * q for unit rows: X = the rows U of jamie_row_normalise, column-centred like the euclidean input (|u - v|^2 does
+ * not change under a shift), G = X X^T, sqnorm = jamie_row_sqnorm(X), rownorm = jamie_row_normalise's norm.  q and its recompute as
+ * in jamie_gram_to_distances (1 - u.v = |u - v|^2 / 2), diagonal exactly 0, exactly symmetric; where either row is a zero row
+ * (rownorm == 0) D = 1 off the diagonal.  scale = 1/2 with centre = 0: sklearn `pairwise_distances(metric='cosine')`; 1/2 with
+ * centre = 1: `pairwise_distances(metric='correlation')`; 1/4 with centre = 1: `(1 - np.corrcoef(X)) / 2` (utilities.distance_matrix
+ * 'pearson').  scale must be positive and finite */
+int jamie_gram_to_scaled_sqdist(float* D, const float* sqnorm, const float* X, long long N, int d, float scale, const float* rownorm,
+                                void* stream);
+/* D[i, j] = sum_c |X[i, c] - X[j, c]| (op = 0) or max_c |X[i, c] - X[j, c]| (op = 1) in fp32 by direct difference over all pairs of
+ * X [N, d], every entry of the N x N buffer written (no Gram matrix): sklearn `pairwise_distances(metric='manhattan' | 'l1' |
+ * 'cityblock')` and `(metric='chebyshev')`.  One chain per pair in ascending c, sums in chunks of 32 features; diagonal exactly 0,
+ * exactly symmetric, exact where the differences and their sums are fp32 numbers.  Any other op returns an error before a launch.
+ * Long pair spaces are split over several launches inside the call */
+int jamie_pairwise_absdiff(const float* X, long long N, int d, int op, float* D, void* stream);
 /* idx[i, 0] = i, idx[i, 1 .. K) = the K - 1 smallest off-diagonal entries of row i of D, ascending (ties: lower column first); radix
  * select on the fp32 bits (D >= 0), survivors sorted.  1 <= K <= min(N, 1024): sklearn
  * `NearestNeighbors(n_neighbors=K).fit(X).kneighbors_graph(X)` (X given explicitly, so the cell is its own first neighbour) */

@@ -202,6 +202,10 @@ EXPORTS = {
     'jamie_dist_workspace': (C.c_longlong, [C.c_longlong]),
     'jamie_row_sqnorm': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_gram_to_distances': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
+    'jamie_row_normalise': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_gram_to_scaled_sqdist': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_void_p,
+                                              C.c_void_p]),
+    'jamie_pairwise_absdiff': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_knn_topk': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_knn_weights': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_knn_graph_init': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -687,6 +691,22 @@ def row_sqnorm(X, out):
 def gram_to_distances(D, sqn, X, squared=False):
     """X: the [N, d] fp32 rows sqn was taken of (near-duplicate pairs are recomputed from them by direct difference)."""
     _call('jamie_gram_to_distances', ptr(D), ptr(sqn), ptr(X), D.shape[0], X.shape[1], int(squared), _stream())
+
+
+def row_normalise(X, centre, out, norm):
+    """X [N, d] fp32 / fp64 -> out [N, d] fp32 unit rows (row-centred first if `centre`), norm [N] fp32 (0: zero / constant row)."""
+    _call('jamie_row_normalise', ptr(X), int(X.dtype == torch.float64), X.shape[0], X.shape[1], int(centre), ptr(out), ptr(norm),
+          _stream())
+
+
+def gram_to_scaled_sqdist(D, sqn, U, scale, rownorm):
+    """U: the [N, d] fp32 (column-centred) unit rows sqn was taken of; D = scale * |u_i - u_j|^2, 1 against a row with rownorm 0."""
+    _call('jamie_gram_to_scaled_sqdist', ptr(D), ptr(sqn), ptr(U), D.shape[0], U.shape[1], float(scale), ptr(rownorm), _stream())
+
+
+def pairwise_absdiff(X, op, D):
+    """op 0: D_ij = sum_c |x_ic - x_jc|; op 1: max_c |x_ic - x_jc|."""
+    _call('jamie_pairwise_absdiff', ptr(X), X.shape[0], X.shape[1], int(op), ptr(D), _stream())
 
 
 def knn_topk(D, K, idx):

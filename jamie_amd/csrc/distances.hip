@@ -1,6 +1,8 @@
 // Stage A of the correspondence path on the MI355X: the cell x cell distance matrices of `compute_distances` (reference
-// jamie.py:839-890) for the euclidean modes and the geodesic mode (kNN graph + all-pairs shortest paths, unioncom's
-// geodesic_distances, jamie_amd/utilities.py).  The host side (jamie_amd/distances.py) centres the columns with
+// jamie.py:839-890) for the euclidean modes, the geodesic mode (kNN graph + all-pairs shortest paths, unioncom's
+// geodesic_distances, jamie_amd/utilities.py), the correlation family (cosine / correlation / pearson: the euclidean Gram pass on
+// unit rows, row_normalise_kernel + tile_pair_kernel<3>) and the L1 family (manhattan / chebyshev: absdiff_kernel, all pairs by
+// direct difference).  The host side (jamie_amd/distances.py) centres the columns with
 // jamie_col_stats / jamie_standardise and forms the Gram matrix G = Xc Xc^T on jamie_gemm_f32_cfg (configuration 17, the exact
 // fp32 pipe) straight into the N x N output; everything below works in that one N x N buffer (row-major, ld = N).
 //
@@ -39,7 +41,10 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict
 //   MODE 0: Gram -> euclidean, D = sqrt(q), q = max(n_i + n_j - 2 G_ij, 0), diagonal exactly 0 (G_ij read from the upper triangle)
 //   MODE 1: Gram -> squared euclidean, D = q
 //   MODE 2: D = min(D, D^T); partial[blk] = largest finite value of the two tiles (0 if none)
-// Modes 0 / 1 recompute q by direct difference, sum_c (x_ic - x_jc)^2 in fp32, where cancellation dominates: q < DIST_TAU (n_i + n_j).
+//   MODE 3: Gram of (column-centred) unit rows -> D = scale * q (1 - u.v = |u - v|^2 / 2: cosine and correlation distance are
+//           q / 2, JAMIE's pearson q / 4); 1 off the diagonal where either row is a zero row (rownorm == 0: sklearn's cosine
+//           leaves a zero row zero)
+// Modes 0 / 1 / 3 recompute q by direct difference, sum_c (x_ic - x_jc)^2 in fp32, where cancellation dominates: q < DIST_TAU (n_i + n_j).
 // n (row_sqnorm_kernel) and G (the MFMA GEMM) round in different orders, so q carries an error of c u (n_i + n_j), u = 2^-24, c ~ 1
 // (a few at d = 2000): on (near-)duplicate cells it swamps q.  A pair that keeps the Gram form has q >= tau s (s = n_i + n_j), so
 // |dD| <= c u s / (2 sqrt(q)) <= c u sqrt(s / tau) / 2; centred data has, for every i, a j with x_i . x_j <= 0, so
@@ -50,7 +55,7 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float* __restrict
 
 template <int MODE>
 __global__ __launch_bounds__(256) void tile_pair_kernel(float* D, long long N, const float* __restrict__ sqn, const float* __restrict__ X,
-                                                        int d, float* partial) {
+                                                        int d, float* partial, float scale, const float* __restrict__ rownorm) {
     const int I = blockIdx.y, J = blockIdx.x;
     const int nt = gridDim.x;
     __shared__ float sA[DIST_PT][DIST_PT + 1], sB[DIST_PT][DIST_PT + 1];
@@ -102,6 +107,10 @@ __global__ __launch_bounds__(256) void tile_pair_kernel(float* D, long long N, c
                 if (tx == l) q = s;
             }
             v = MODE == 0 ? sqrtf(q) : q;
+            if (MODE == 3) {
+                v = scale * q;
+                if (ok && i != j && (rownorm[i] == 0.f || rownorm[j] == 0.f)) v = 1.f;
+            }
         }
         if (!ok) continue;
         D[i * N + j] = v;
@@ -134,6 +143,194 @@ __global__ __launch_bounds__(256) void fill_unreachable_kernel(float* D, long lo
     const float fill = 2.f * maxv[0];
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256)
         if (!(D[e] < d_inf())) D[e] = fill;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Unit rows for the correlation family (the host side column-centres them before the Gram pass: |u - v|^2 does not change under a
+// shift, and all-positive rows such as counts are nearly parallel -- G ~ 1 everywhere, where a d = 2000 fma chain loses 1e-5):
+// out[i, :] = (x_i - m_i) / |x_i - m_i| as fp32, m_i = the row's mean (centre = 1) or 0.
+// Mean, norm and the quotient are taken in fp64 with one rounding to fp32 at the store (as jamie_col_stats / jamie_standardise do
+// for columns).  norm[i] = that norm as fp32, exactly 0 for a row the host cannot normalise -- a zero row, or with centre = 1 a
+// constant row (every entry equal; tested on the entries, not on the rounded norm) -- and such a row is written as zeros.
+// One wave per row, fixed reduction order: deterministic.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);       // (lane l and lane l ^ o add the same two numbers: uniform result)
+    return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void row_normalise_kernel(const T* __restrict__ X, long long N, int d, int centre,
+                                                            float* __restrict__ out, float* __restrict__ norm) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= N) return;
+    const T* x = X + row * d;
+    double mean = 0.0;
+    bool flat = false;
+    if (centre) {
+        const T x0 = x[0];
+        double s = 0.0;
+        bool differs = false;
+        for (int c = lane; c < d; c += 64) {
+            s += (double)x[c];
+            differs |= x[c] != x0;
+        }
+        mean = wave_sum_f64(s) / (double)d;
+        flat = __ballot(differs) == 0ull;
+    }
+    double q = 0.0;
+    for (int c = lane; c < d; c += 64) {
+        const double t = (double)x[c] - mean;
+        q += t * t;
+    }
+    const double nrm = flat ? 0.0 : sqrt(wave_sum_f64(q));
+    float* o = out + row * d;
+    for (int c = lane; c < d; c += 64) o[c] = nrm > 0.0 ? (float)(((double)x[c] - mean) / nrm) : 0.f;
+    if (lane == 0) norm[row] = nrm > 0.0 ? fmaxf((float)nrm, 0x1p-126f) : 0.f;      // (a tiny norm must not read as a zero row)
+}
+
+// ------------------------------------------------------------------------------------------------
+// L1 family: D_ij = sum_c |x_ic - x_jc| (OP 0) or max_c |x_ic - x_jc| (OP 1) over all pairs of one [N, d] fp32 matrix, by direct
+// difference, written straight into the N x N output.  The tile shape is the pair tile of csrc/metrics.hip: 256 threads own
+// 128 x 128 pairs, a thread 8 x 8 of them (rows (r / 4) * 64 + ty * 4 + r % 4, columns (s / 4) * 64 + tx * 4 + s % 4); both operands
+// are staged feature-major in LDS, AD_KC = 32 features per trip, and read back as ds_read_b128 (rows: broadcast; columns: 16
+// contiguous 16-byte slots).  Per pair and feature: v_sub_f32 + v_add_f32 (v_max_f32) with the |.| source modifier -- VALU-issue
+// bound, hence the two workgroups per CU of the launch bounds.
+// One chain per pair in ascending c; OP 0 sums every trip into a fresh partial and adds the partial to the total (chunks of 32:
+// the error of a d = 2000 sum drops from 2.7e-6 to 4.8e-7 max D).  |a - b| == |b - a| and x - x == 0, so the diagonal is exactly 0
+// and the matrix exactly symmetric; features past d and rows past N are staged as 0 and add |0 - 0| = 0.  Exact on data whose
+// differences and sums are fp32 numbers (integers).
+// Only the tiles I <= J are computed.  A tile leaves through LDS, 64 rows at a time, so that the stores of both the tile and its
+// mirror image walk along rows of D: the direct half-tile is written row-major (8 lanes of a ds_write_b128 group: 32 contiguous
+// dwords), the mirror half-tile with its LDS rows permuted, local column tx * 4 + k in LDS row k * 16 + tx, so that the 8 lanes of
+// a group are AD_LD = 132 dwords apart: banks 4 tx .. 4 tx + 3, conflict-free (unpermuted they would be 528 apart: two banks of 8).
+// ------------------------------------------------------------------------------------------------
+#define AD_KC 32
+#define AD_T 128
+#define AD_LD (AD_T + 4)
+#define AD_LAUNCH_WORK 4000000000000ll      // pair-features per launch (a fraction of a second)
+
+// rows [r0, r0 + 128) x features [c0, c0 + 32) of X [N, d] -> S[feature][row], zero where the row or the feature does not exist
+__device__ __forceinline__ void ad_stage(const float* __restrict__ X, long long N, long long r0, int d, int c0, bool vec,
+                                         float* __restrict__ S) {
+    for (int s = threadIdx.x; s < AD_T * (AD_KC / 4); s += 256) {
+        const int r = s >> 3, c = c0 + (s & 7) * 4;
+        const long long gr = r0 + r;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (gr < N) {
+            const float* p = X + gr * d + c;
+            if (vec && c + 3 < d) {
+                const float4 x = *reinterpret_cast<const float4*>(p);
+                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c + k < d) v[k] = p[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S[((s & 7) * 4 + k) * AD_LD + r] = v[k];
+    }
+}
+
+// 64 x 128 floats of LDS (row stride AD_LD) -> rows gi0 + row(p), columns gj0 .. gj0 + 127 of D; a wave stores 64 consecutive floats
+template <bool PERMUTED>
+__device__ __forceinline__ void ad_store_rows(const float* __restrict__ S, float* __restrict__ D, long long N, long long gi0,
+                                              long long gj0) {
+    for (int e = threadIdx.x; e < 64 * AD_T; e += 256) {
+        const int p = e >> 7, c = e & 127;
+        const long long gi = gi0 + (PERMUTED ? (p & 15) * 4 + (p >> 4) : p), gj = gj0 + c;
+        if (gi < N && gj < N) D[gi * N + gj] = S[p * AD_LD + c];
+    }
+}
+
+// acc (+ or max)= |a - b|.  The accumulate is spelled out: from `acc + fabsf(t)` hipcc's SLP vectoriser makes v_pk_add_f32 pairs, which
+// have no |.| modifier (two v_and_b32 beside every packed add) and issue at half the rate of a plain VALU instruction: 1.5 times the
+// issue cycles; from fmaxf it adds a canonicalising v_max_f32 per value.
+template <int OP>
+__device__ __forceinline__ void ad_step(float& acc, float a, float b) {
+    const float t = a - b;
+    if (OP == 0) asm("v_add_f32_e64 %0, |%1|, %0" : "+v"(acc) : "v"(t));
+    else asm("v_max_f32_e64 %0, |%1|, %0" : "+v"(acc) : "v"(t));
+}
+
+template <int OP>
+__global__ __launch_bounds__(256, 2) void absdiff_kernel(const float* __restrict__ X, long long N, int d, int vec, long long tile_i0,
+                                                         float* __restrict__ D) {
+    const long long I = tile_i0 + blockIdx.y, J = blockIdx.x;
+    if (J < I) return;
+    __shared__ __attribute__((aligned(16))) float smem[2 * AD_KC * AD_LD];      // the staged operands, then 64 x AD_LD of output
+    float* Xs = smem;
+    float* Ys = I == J ? smem : smem + AD_KC * AD_LD;                           // (a diagonal tile stages its rows once)
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const long long i0 = I * AD_T, j0 = J * AD_T;
+    float acc[8][8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int s = 0; s < 8; ++s) acc[r][s] = 0.f;
+    for (int c0 = 0; c0 < d; c0 += AD_KC) {
+        __syncthreads();                                   // the last trip's reads are done
+        ad_stage(X, N, i0, d, c0, vec != 0, Xs);
+        if (I != J) ad_stage(X, N, j0, d, c0, vec != 0, Ys);
+        __syncthreads();
+        const int rest = (d - c0 + 3) & ~3;
+        const int kc = rest < AD_KC ? rest : AD_KC;
+        float part[8][8];
+        if (OP == 0) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+#pragma unroll
+                for (int s = 0; s < 8; ++s) part[r][s] = 0.f;
+        }
+#pragma unroll 2
+        for (int c = 0; c < kc; ++c) {
+            float a[8], b[8];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const float4 x = *reinterpret_cast<const float4*>(&Xs[c * AD_LD + m * 64 + ty * 4]);
+                a[m * 4] = x.x; a[m * 4 + 1] = x.y; a[m * 4 + 2] = x.z; a[m * 4 + 3] = x.w;
+                const float4 y = *reinterpret_cast<const float4*>(&Ys[c * AD_LD + m * 64 + tx * 4]);
+                b[m * 4] = y.x; b[m * 4 + 1] = y.y; b[m * 4 + 2] = y.z; b[m * 4 + 3] = y.w;
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+#pragma unroll
+                for (int s = 0; s < 8; ++s) ad_step<OP>(OP == 0 ? part[r][s] : acc[r][s], a[r], b[s]);
+        }
+        if (OP == 0) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+#pragma unroll
+                for (int s = 0; s < 8; ++s) acc[r][s] += part[r][s];
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                          // rows h * 64 .. of the tile (I, J)
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+                *reinterpret_cast<float4*>(&smem[(ty * 4 + r) * AD_LD + m * 64 + tx * 4]) =
+                    make_float4(acc[h * 4 + r][m * 4], acc[h * 4 + r][m * 4 + 1], acc[h * 4 + r][m * 4 + 2], acc[h * 4 + r][m * 4 + 3]);
+        __syncthreads();
+        ad_store_rows<false>(smem, D, N, i0 + h * 64, j0);
+    }
+    if (I == J) return;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {                          // columns m * 64 .. of the tile = rows of the tile (J, I)
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                *reinterpret_cast<float4*>(&smem[(k * 16 + tx) * AD_LD + h * 64 + ty * 4]) =
+                    make_float4(acc[h * 4][m * 4 + k], acc[h * 4 + 1][m * 4 + k], acc[h * 4 + 2][m * 4 + k], acc[h * 4 + 3][m * 4 + k]);
+        __syncthreads();
+        ad_store_rows<true>(smem, D, N, j0 + m * 64, i0);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -460,9 +657,47 @@ extern "C" int jamie_row_sqnorm(const float* X, long long N, int d, float* out, 
 extern "C" int jamie_gram_to_distances(float* D, const float* sqnorm, const float* X, long long N, int d, int squared, void* stream) {
     JAMIE_ARG(D && sqnorm && X && N > 0 && N <= (1 << 24) && d > 0, "null pointer / 0 < N <= 2^24 / d > 0");
     const int nt = dist_tiles(N);
-    if (squared) hipLaunchKernelGGL(tile_pair_kernel<1>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr);
-    else hipLaunchKernelGGL(tile_pair_kernel<0>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr);
+    if (squared) hipLaunchKernelGGL(tile_pair_kernel<1>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr,
+                                     1.f, nullptr);
+    else hipLaunchKernelGGL(tile_pair_kernel<0>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr, 1.f, nullptr);
     return jamie_launch_status("jamie_gram_to_distances");
+}
+
+extern "C" int jamie_gram_to_scaled_sqdist(float* D, const float* sqnorm, const float* X, long long N, int d, float scale,
+                                           const float* rownorm, void* stream) {
+    JAMIE_ARG(D && sqnorm && X && rownorm && N > 0 && N <= (1 << 24) && d > 0, "null pointer / 0 < N <= 2^24 / d > 0");
+    JAMIE_ARG(scale > 0.f && scale < __builtin_inff(), "scale must be positive and finite");
+    const int nt = dist_tiles(N);
+    hipLaunchKernelGGL(tile_pair_kernel<3>, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, D, N, sqnorm, X, d, nullptr, scale,
+                       rownorm);
+    return jamie_launch_status("jamie_gram_to_scaled_sqdist");
+}
+
+extern "C" int jamie_row_normalise(const void* X, int is_f64, long long N, int d, int centre, float* out, float* norm, void* stream) {
+    JAMIE_ARG(X && out && norm && N > 0 && d > 0, "null pointer / empty");
+    JAMIE_ARG((is_f64 == 0 || is_f64 == 1) && (centre == 0 || centre == 1), "is_f64 and centre are 0 or 1");
+    const dim3 grid((unsigned)((N + 3) / 4));
+    if (is_f64)
+        hipLaunchKernelGGL(row_normalise_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)X, N, d, centre, out, norm);
+    else
+        hipLaunchKernelGGL(row_normalise_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)X, N, d, centre, out, norm);
+    return jamie_launch_status("jamie_row_normalise");
+}
+
+extern "C" int jamie_pairwise_absdiff(const float* X, long long N, int d, int op, float* D, void* stream) {
+    JAMIE_ARG(X && D && N > 0 && N <= (1 << 24) && d > 0, "null pointer / 0 < N <= 2^24 / d > 0");
+    JAMIE_ARG(op == 0 || op == 1, "op is 0 (sum) or 1 (max)");
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = (d % 4 == 0) && ((uintptr_t)X & 15) == 0;
+    const long long nt = (N + AD_T - 1) / AD_T;
+    long long step = AD_LAUNCH_WORK / ((long long)AD_T * N * d);            // rows of tiles per launch
+    step = step < 1 ? 1 : (step > 65535 ? 65535 : step);
+    for (long long t0 = 0; t0 < nt; t0 += step) {
+        const long long n = nt - t0 < step ? nt - t0 : step;
+        if (op == 0) hipLaunchKernelGGL(absdiff_kernel<0>, dim3((unsigned)nt, (unsigned)n), dim3(256), 0, st, X, N, d, vec, t0, D);
+        else hipLaunchKernelGGL(absdiff_kernel<1>, dim3((unsigned)nt, (unsigned)n), dim3(256), 0, st, X, N, d, vec, t0, D);
+    }
+    return jamie_launch_status("jamie_pairwise_absdiff");
 }
 
 extern "C" int jamie_knn_topk(const float* D, long long N, int K, int32_t* idx, void* stream) {
@@ -508,7 +743,7 @@ extern "C" int jamie_apsp_finalise(float* D, long long N, float* partials, long 
     const int nt = dist_tiles(N);
     JAMIE_ARG(n_partials >= (long long)nt * nt, "n_partials < jamie_dist_workspace(N)");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tile_pair_kernel<2>, dim3(nt, nt), dim3(256), 0, st, D, N, nullptr, nullptr, 0, partials);
+    hipLaunchKernelGGL(tile_pair_kernel<2>, dim3(nt, nt), dim3(256), 0, st, D, N, nullptr, nullptr, 0, partials, 1.f, nullptr);
     hipLaunchKernelGGL(max_reduce_kernel, dim3(1), dim3(256), 0, st, partials, (long long)nt * nt, maxv);
     const long long blocks = (N * N + 255) / 256;
     hipLaunchKernelGGL(fill_unreachable_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, D, N * N, maxv);

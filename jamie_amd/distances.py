@@ -1,15 +1,24 @@
 """Stage A of the correspondence path on the MI355X: the cell x cell distance matrices of `compute_distances` (reference
-jamie.py:839-890) for the euclidean modes and the geodesic mode (`utilities.geodesic_distances`), as float32 device tensors.
+jamie.py:839-890) for the euclidean modes, the geodesic mode (`utilities.geodesic_distances`), the correlation family and the L1
+family, as float32 device tensors.
 
     euclidean(X, squared=False)   sklearn pairwise_distances(metric='euclidean' | 'sqeuclidean')
     knn(X, k)                     sklearn NearestNeighbors(k).kneighbors_graph(X, mode='distance'), as (idx, w) [N, k]
     geodesic(X, kmax)             utilities.geodesic_distances(X, kmax), step for step
+    cosine(X), correlation(X)     sklearn pairwise_distances(metric='cosine' | 'correlation')
+    pearson(X)                    (1 - np.corrcoef(X)) / 2 (utilities.distance_matrix 'pearson')
+    manhattan(X), chebyshev(X)    sklearn pairwise_distances(metric='manhattan' (= 'l1', 'cityblock') | 'chebyshev')
 
 The kernels are in csrc/distances.hip (include/jamie_hip.h, "Stage A distances on the device").  The columns are centred first
 (distances do not change under a shift; centring cuts the cancellation of the Gram form), G = Xc Xc^T is the exact-fp32 GEMM
 (configuration 17) written straight into the N x N result, which every later pass then works on in place: peak device memory
 N^2 * 4 bytes plus O(N (d + K)).  The only host work is the geodesic growth loop's connectivity test: scipy's
 `connected_components` on the N x k neighbour list, the same call the host path makes.
+
+The correlation family is that Gram pass on unit rows (1 - u.v = |u - v|^2 / 2).  jamie_row_normalise takes X as it is -- these
+distances change under a column shift of X -- and the unit rows are then column-centred like the euclidean input: on all-positive
+data (counts) they are nearly parallel, and the uncentred Gram form would lose 1e-5 at d = 2000.  The L1 family has no Gram form: jamie_pairwise_absdiff takes all pairs by direct
+difference.
 """
 import math
 
@@ -71,6 +80,81 @@ def _euclidean_centred(Xc, squared=False, out=None):
 def euclidean(X, squared=False, device='cuda'):
     """[N, N] float32 device tensor of euclidean (or squared euclidean) distances; diagonal exactly 0, exactly symmetric."""
     return _euclidean_centred(centred(X, device), squared)
+
+
+def _unit_row_distances(X, centre, scale, name, device):
+    """scale * |u_i - u_j|^2 on the unit rows of X (row-centred first if `centre`)."""
+    t = _device_input(X, device)
+    N, d = t.shape
+    if N == 1:
+        return torch.zeros(1, 1, dtype=torch.float32, device=t.device)
+    U = torch.empty(N, d, dtype=torch.float32, device=t.device)
+    norm = torch.empty(N, dtype=torch.float32, device=t.device)
+    nv.row_normalise(t, centre, U, norm)
+    if centre:
+        flat = torch.nonzero(norm == 0)
+        if flat.numel():
+            raise ValueError(f'{name}: row {int(flat[0])} is constant, its correlation with any row is undefined (the host path '
+                             f'returns NaN)')
+    del t
+    Uc = centred(U, device)                    # columns: the Gram form then cancels as little as the euclidean one
+    del U
+    D = torch.empty(N, N, dtype=torch.float32, device=Uc.device)
+    nv.gemm([nv.gemm_problem(Uc, Uc, D, N, N, d, d, d, N)], nv.NT, GRAM_CFG)           # G = Uc Uc^T
+    sqn = torch.empty(N, dtype=torch.float32, device=Uc.device)
+    nv.row_sqnorm(Uc, sqn)
+    nv.gram_to_scaled_sqdist(D, sqn, Uc, scale, norm)
+    return D
+
+
+def cosine(X, device='cuda'):
+    """[N, N] float32 device tensor of cosine distances 1 - x_i.x_j / (|x_i| |x_j|); diagonal exactly 0, exactly symmetric.  A zero
+    row is at distance 1 from every other row, as in sklearn."""
+    return _unit_row_distances(X, False, 0.5, 'cosine', device)
+
+
+def correlation(X, device='cuda'):
+    """[N, N] float32 device tensor of correlation distances 1 - r_ij (r: Pearson correlation of rows i and j).  A constant row
+    raises ValueError."""
+    return _unit_row_distances(X, True, 0.5, 'correlation', device)
+
+
+def pearson(X, device='cuda'):
+    """[N, N] float32 device tensor of (1 - r_ij) / 2, JAMIE's 'pearson' mode.  A constant row raises ValueError."""
+    return _unit_row_distances(X, True, 0.25, 'pearson', device)
+
+
+def _absdiff_rows(X, device):
+    """The fp32 rows the L1 family takes differences of.  Values that are fp32 numbers already go in as they are: their
+    differences then round once (integers: not at all).  Anything else is column-centred in fp64 first (the L1 family does not
+    change under a column shift), which keeps the conversion to fp32 from eating the differences."""
+    t = _device_input(X, device)
+    if t.dtype == torch.float32:
+        return t
+    t32 = t.to(torch.float32)
+    if bool((t32.to(torch.float64) == t).all()):
+        return t32
+    del t32
+    return centred(t, device)
+
+
+def _absdiff(X, op, device):
+    Xr = _absdiff_rows(X, device)
+    N = Xr.shape[0]
+    D = torch.empty(N, N, dtype=torch.float32, device=Xr.device)
+    nv.pairwise_absdiff(Xr, op, D)
+    return D
+
+
+def manhattan(X, device='cuda'):
+    """[N, N] float32 device tensor of L1 distances sum_c |x_ic - x_jc| ('manhattan' = 'l1' = 'cityblock'); diagonal exactly 0,
+    exactly symmetric."""
+    return _absdiff(X, 0, device)
+
+
+def chebyshev(X, device='cuda'):
+    """[N, N] float32 device tensor of Chebyshev distances max_c |x_ic - x_jc|; diagonal exactly 0, exactly symmetric."""
+    return _absdiff(X, 1, device)
 
 
 def k_max(N, kmax):

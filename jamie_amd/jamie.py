@@ -27,7 +27,8 @@ _DISTANCE_MODES = [
     'rogerstanimoto', 'russellrao', 'seuclidean', 'sokalmichener', 'sokalsneath', 'sqeuclidean', 'yule',
     'wminkowski', 'nan_euclidean', 'haversine', 'geodesic', 'spearman', 'pearson']
 # the modes of distances='device' (jamie_amd/distances.py)
-_DEVICE_DISTANCE_MODES = ('geodesic', 'euclidean', 'l2', 'sqeuclidean')
+_DEVICE_DISTANCE_MODES = ('geodesic', 'euclidean', 'l2', 'sqeuclidean', 'cosine', 'correlation', 'pearson', 'manhattan', 'l1',
+                          'cityblock', 'chebyshev')
 
 
 def init_random_seed(manual_seed):
@@ -66,9 +67,11 @@ class JAMIE:
       grad_comm_dtype 'auto' (default: the compute dtype), 'f32' or 'bf16': precision of the gradient all-reduce
                    messages when distributed (bf16 halves the 4 P bytes exchanged per step)
       distances    'host' (default): stage A (`compute_distances`) on the host in float64 with scipy / sklearn, as the reference;
-                   'device': on the MI355X (jamie_amd/distances.py) in fp32 for distance_mode 'geodesic', 'euclidean', 'l2' and
-                   'sqeuclidean' (any other mode raises ValueError): `self.dist` then holds float32 device tensors that go
-                   straight into Prime_Dual, so no N x N matrix crosses PCIe
+                   'device': on the MI355X (jamie_amd/distances.py) in fp32 for distance_mode 'geodesic', 'euclidean', 'l2',
+                   'sqeuclidean', 'cosine', 'correlation', 'pearson', 'manhattan' / 'l1' / 'cityblock' and 'chebyshev' (any other
+                   mode, 'spearman' included, raises ValueError; so does a constant row under 'correlation' / 'pearson', where
+                   the host path returns NaN): `self.dist` then holds float32 device tensors that go straight into Prime_Dual,
+                   so no N x N matrix crosses PCIe
       metrics      'host' (default): `test_closer` / `test_LabelTA` on the host with sklearn in float64, as the reference (a
                    2N x 2N distance matrix: a few thousand cells at most); 'device': on the MI355X (jamie_amd/metrics.py)
                    in fp32 without any N x N matrix, euclidean only, for whole data sets
@@ -142,7 +145,7 @@ class JAMIE:
             raise TypeError(f'unexpected keyword arguments: {sorted(kwargs)}')
         if self.distances == 'device' and self.distance_mode not in _DEVICE_DISTANCE_MODES:
             raise ValueError(f"distances='device' supports distance_mode {', '.join(map(repr, _DEVICE_DISTANCE_MODES))}; "
-                             f'got {self.distance_mode!r}')
+                             f"got {self.distance_mode!r} (use distances='host')")
         self.model = None
         self.engine = None
         self.loss_history = {}
@@ -215,9 +218,13 @@ class JAMIE:
         mode = self.distance_mode
         if mode not in _DEVICE_DISTANCE_MODES:
             raise ValueError(f"distances='device' supports distance_mode {', '.join(map(repr, _DEVICE_DISTANCE_MODES))}; "
-                             f'got {mode!r}')
+                             f"got {mode!r} (use distances='host')")
         if mode == 'geodesic':
             return lambda df: jdist.geodesic(df, self.kmax, device=self.device)            # noqa: E731
+        other = {'cosine': jdist.cosine, 'correlation': jdist.correlation, 'pearson': jdist.pearson, 'manhattan': jdist.manhattan,
+                 'l1': jdist.manhattan, 'cityblock': jdist.manhattan, 'chebyshev': jdist.chebyshev}.get(mode)
+        if other is not None:
+            return lambda df: other(df, device=self.device)                                # noqa: E731
         return lambda df: jdist.euclidean(df, squared=mode == 'sqeuclidean', device=self.device)   # noqa: E731
 
     def Prime_Dual(self, dist, dx=None, dy=None, verbose=True):
