@@ -318,7 +318,11 @@ long long jamie_latent_m_colpart_size(int B, int L);
  * (clip_grad_norm_(params, 1) + optim.Adam.step + zero_grad, jamie.py:739-741).
  * `state` = device uint64[4] shared with `rng`: state[1] (step) is incremented by jamie_grad_sqnorm.
  * hyper (device float[16], shared with jamie_latent): [8] lr, [9] beta1, [10] beta2, [11] eps, [12] max_norm,
- * [13] grad_scale (1/world_size: the all-reduced SUM is averaged inside the update).
+ * [13] grad_scale (1/world_size: the all-reduced SUM is averaged inside the update),
+ * [14] 1 - beta1, [15] 1 - beta2: formed in double by the host and rounded once, as torch.optim.Adam forms them (1 - 0.999 rounds
+ * to 0.001f; 1.f - fl32(0.999) is 1.29e-5 smaller).  Used for the moment updates and, as 1 - (double)hyper[14|15], for the bias
+ * corrections.  A slot that is 0 means "not given": the kernel then forms 1.f - beta itself.
+ * A NaN gradient norm gives a NaN clip coefficient (every p, m, v becomes NaN), as clip_grad_norm_ does.
  * ------------------------------------------------------------------------------------------- */
 int jamie_optim_blocks(long long n);   /* number of partials jamie_grad_sqnorm writes for n elements */
 int jamie_grad_sqnorm(const float* g, long long n, float* partials, int n_partials, uint64_t* state,

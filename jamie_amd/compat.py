@@ -70,7 +70,7 @@ class edModelVarTorch(torch.nn.Module):
 
     def _engine_for(self, B):
         if B not in self._engines:
-            eng = TrainEngine(self.inner, B, loss_weights=[0, 0, 0, 0])   # losses are the caller's
+            eng = TrainEngine(self.inner, B, loss_weights=[0, 0, 0, 0], torch_one_minus_beta=True)   # losses are the caller's
             eng.hyper[:4] = 0
             self._engines[B] = eng
         return self._engines[B]

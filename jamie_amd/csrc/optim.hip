@@ -145,9 +145,12 @@ __global__ __launch_bounds__(T) void clip_adam_kernel(float* __restrict__ p, con
     for (int u = 0; u < 8; ++u) t0[u] = (int)threadIdx.x + u * T < n_partials ? partials[threadIdx.x + u * T] : 0.f;
     const float lr = hyper[8], b1 = hyper[9], b2 = hyper[10], eps = hyper[11], max_norm = hyper[12];
     const float gscale = hyper[13];
+    // 1 - beta as the host formed it in double and rounded once (torch's 1 - 0.999 is 0.001f; 1.f - fl32(0.999) is 1.29e-5 off
+    // it, on every increment of v and in the bias correction); 0 = not given: formed here from the rounded beta
+    const float o1 = hyper[14], o2 = hyper[15];
     const double t = (double)state[1];
-    const float bc1 = (float)(1.0 - pow((double)b1, t));
-    const float bc2s = (float)sqrt(1.0 - pow((double)b2, t));
+    const float bc1 = (float)(1.0 - pow(o1 != 0.f ? 1.0 - (double)o1 : (double)b1, t));
+    const float bc2s = (float)sqrt(1.0 - pow(o2 != 0.f ? 1.0 - (double)o2 : (double)b2, t));
     const float step_size = lr / bc1;
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += t0[u];
@@ -160,8 +163,10 @@ __global__ __launch_bounds__(T) void clip_adam_kernel(float* __restrict__ p, con
     }
     s = block_sum(s, red);
     const float total = sqrtf(s) * gscale;                 // norm of the (averaged) gradient
-    const float coef = fminf(max_norm / (total + 1e-6f), 1.0f) * gscale;
-    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    // fminf drops a NaN operand: a NaN norm must give a NaN coefficient (clip_grad_norm_ clamps NaN to NaN), not an unclipped step
+    const float clip = fminf(max_norm / (total + 1e-6f), 1.0f);
+    const float coef = (total != total ? total : clip) * gscale;
+    const float omb1 = o1 != 0.f ? o1 : 1.f - b1, omb2 = o2 != 0.f ? o2 : 1.f - b2;
     auto upd = [&](float& pp, float gg, float& mm, float& vv) {
         gg *= coef;
         mm = mm + (gg - mm) * omb1;                        // exp_avg.lerp_(grad, 1 - beta1)

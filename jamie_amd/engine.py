@@ -63,6 +63,7 @@ def tune(**kw):
 # hyper buffer slots (device float[16]; see include/jamie_hip.h)
 H_KL, H_REC, H_ALIGN, H_F = 0, 1, 2, 3
 H_LR, H_B1, H_B2, H_EPS, H_MAXNORM, H_GSCALE = 8, 9, 10, 11, 12, 13
+H_OMB1, H_OMB2 = 14, 15
 
 
 def choose_splitk(M, N, K, bm=64, bn=64):
@@ -272,7 +273,8 @@ def kl_anneal(epoch, min_epochs, epoch_DNN):
 
 class TrainEngine:
     def __init__(self, model, batch_size, lr=1e-3, loss_weights=None, dist_method='euclidean', seed=666,
-                 world_size=1, compute_dtype='f32', dx_from_weights=True, skinny_tr=True, grad_bf16=None):
+                 world_size=1, compute_dtype='f32', dx_from_weights=True, skinny_tr=True, grad_bf16=None,
+                 torch_one_minus_beta=False):
         """compute_dtype 'f32': exact-fp32 MFMA GEMMs (the parity configuration).  'bf16': bf16 MFMA GEMMs with
         fp32 accumulation, fp32 master weights / optimiser / BatchNorm / losses (BASELINE config 2); needs every
         feature count, the latent size and the batch size to be multiples of 8."""
@@ -321,6 +323,10 @@ class TrainEngine:
                                                      self.loss_weights[3])
         hyper[H_LR], hyper[H_B1], hyper[H_B2], hyper[H_EPS] = lr, 0.9, 0.999, 1e-8
         hyper[H_MAXNORM], hyper[H_GSCALE] = 1.0, 1.0 / world_size
+        if torch_one_minus_beta:
+            # 1 - beta formed in double and rounded once, as torch.optim.Adam forms them: 1 - 0.999 is 0.001f there, the kernel's own
+            # 1.f - fl32(0.999) makes every increment of v 1.29e-5 smaller.  The facades (jamie.py, compat.py) ask for it
+            hyper[H_OMB1], hyper[H_OMB2] = 1 - 0.9, 1 - 0.999
         self._hyper_host = hyper
         self.hyper = hyper.to(self.dev)
         self.set_kl_anneal(1.0)

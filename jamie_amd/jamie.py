@@ -412,7 +412,7 @@ class JAMIE:
         self.PF_Ratio = 1 if self.PF_Ratio is None else self.PF_Ratio        # jamie.py:517
         eng = TrainEngine(self.model, B, lr=self.model_lr, loss_weights=self.loss_weights,
                           dist_method=self.dist_method, seed=int(self.manual_seed) + 7919 * rank,
-                          world_size=world, compute_dtype=self.compute_dtype)
+                          world_size=world, compute_dtype=self.compute_dtype, torch_one_minus_beta=True)
         eng.accumulate = False
         if not self.batch_step:
             eng.set_grad_bf16(False)        # gradients accumulate over the batches of an epoch (jamie.py:734-749): fp32 buffer
