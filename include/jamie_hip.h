@@ -170,9 +170,25 @@ typedef struct {
     float* save_mean; float* save_invstd;            /* [N] each, for the backward pass             */
     float* out;                                      /* [B,N] activation after dropout              */
     const uint8_t* mask;                             /* explicit 0/1 keep mask [B,N] or NULL (RNG)  */
-    int B, N; int rng_stream;
+    int B, N;
+    int rng_stream;                                  /* dropout without `mask`: element (row, col) is kept iff a 16-bit half of
+                                                      * one Philox4x32-10 word is >= thr = trunc(p * 65536) (fp32 product,
+                                                      * clamped to [0, 65535]):
+                                                      *   counter = (rk, col >> 2, rng_stream, low 32 bits of rng[1] = step),
+                                                      *             rk = (row & 127) | ((row >> 8) << 7)
+                                                      *   key     = (low 32 bits of rng[0] = seed, high 32 bits of seed XOR high
+                                                      *             32 bits of step)
+                                                      *   word col & 3 of the output, its half (row >> 7) & 1 (0: bits 0..15)
+                                                      * -- one call serves a quad of columns in rows r and r + 128.  Every kernel
+                                                      * (dword / float4, forward / backward) draws the same bit for the same
+                                                      * element (tests/bn_util.py keep_mask, tests/test_hip_bn.py).  The keep
+                                                      * probability is 1 - trunc(p * 65536) / 65536 (0.4000092 at p = 0.6) while
+                                                      * the survivors are scaled by 1 / (1 - p) */
     void* out_bf16;                                  /* optional bf16 [B,N] copy of `out` (out may be NULL) */
-    void* outT_bf16;                                 /* optional bf16 transposed [N,B] copy (B <= 512, B % 8 == 0) */
+    void* outT_bf16;                                 /* optional bf16 transposed [N,B] copy.  Either bf16 copy: B % 8 == 0, and
+                                                      * B <= 1024 on the float4 path (N % 4 == 0, slab_stride % 4 == 0, aligned
+                                                      * pointers; the transposed tile is 16 x (128 R + 2) shorts of LDS, R = 4 or
+                                                      * 8), B <= 512 on the dword path; anything else is an argument error */
     int panel;                                       /* 1: `h` (every slab, and the sum written back to slab 0) is in panels of
                                                       * JAMIE_PANEL columns (jamie_gemm_problem.c_panel); float4 kernels only
                                                       * (B <= 1024, N % 4 == 0); `out` / the bf16 copies / `mask` stay row-major */
