@@ -619,13 +619,8 @@ def corr_from_indices(idx0, idx1, corr):
 
 def colsum_group(items, accumulate=False):
     """items: list of (X [M, N] contiguous fp32, out [N]) - one launch for all (bias gradients of both modalities)."""
-    probs = []
-    for X, out in items:
-        p = ColsumProblem()
-        p.X, p.out, p.M, p.N, p.ld, p.nslab, p.slab_stride, p.accumulate = ptr(X), ptr(out), X.shape[0], X.shape[1], X.shape[1], 1, 0, int(accumulate)
-        probs.append(p)
-    arr = (ColsumProblem * len(probs))(*probs)
-    _call('jamie_colsum_group', arr, len(probs), _stream())
+    arr, count, _ = colsum_problems(items, accumulate)
+    _call('jamie_colsum_group', arr, count, _stream())
 
 
 def csr_block(indptr, indices, vals, idx0, idx1, out, row_off=0, col_off=0, normalise=True):

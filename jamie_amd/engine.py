@@ -18,46 +18,36 @@ KL_WEIGHT = 32 * 1e-3       # jamie.py:632
 ALIGN_WEIGHT = 32           # jamie.py:658
 LOSS_NAMES = ['KL', 'Rec', 'CosSim', 'F']
 
-# Tuning knobs of the launch plans and the older variant of every adopted change, for A/B measurements on one box
-# (tools/ab.sh "JAMIE_TUNE=key=value+key=value" -> bench.py --tune; profiles/r0*_ab_*.log).  NOT read from the environment: the package reads
-# no JAMIE_* variable besides the library path and the two test hooks of distributed.py (tests/test_host_cpu.py asserts it).
-# Set them with engine.tune(key=value, ...) BEFORE an engine is built.
+# Tuning knobs of the launch plans, for A/B measurements on one box (tools/ab.sh "JAMIE_TUNE=key=value+key=value" -> bench.py --tune;
+# profiles/r0*_ab_*.log).  NOT read from the environment: the package reads no JAMIE_* variable besides the library path and the two
+# test hooks of distributed.py (tests/test_host_cpu.py asserts it).  Set them with engine.tune(key=value, ...); a TrainEngine keeps
+# the values it was built under (its buffers are laid out from them), whatever tune() is given afterwards.  The switches that
+# selected the older variant of an adopted change are gone: EXPERIMENTS.md, "Retired A/B switches", names each one's log.
 TUNING = {
     'bf16_rows': None,            # "cfg:s0,s1[;cfg:s0,s1 for the N < K launches]": tile configuration + K slices of the bf16 forward launches
     'f32_rows': None,             # "[cfg:]s0,s1[;...]": the same for the fp32 forward / dX launches
-    'bwd_k_per_slab': 1700.0,     # K per split-K slab of the bf16 dX products
-    'sk_skinny': None,            # slab count of the skinny head / latent products
     'f32_dw_cfg': None, 'f32_dx_cfg': None,      # fp32 tile configurations of the dW / dX launches
-    'f32_dw_small_cfg': None,     # ... of the skinny layers' dW launch (decoder layer 0, heads)
     'f32_rows_cfg': None,         # ... of the planned forward / dX launches (the planner's K slices stay)
-    'prefetch': 1,                # bf16 mode, BatchNorm prefetch riders: 0 off, 1 the next product's weights
-    'stagger': True,              # flat optimiser buffers start 4 KB apart
-    'f32_dx_plan': True, 'f32_fused_norm': True,
+    'f32_dx_plan': True,
     'f32_x3': True,               # fp32 mode: the large products on the bf16 matrix pipe, every fp32 element cut into three bf16 pieces
                                   # (gemm_f32.hip configuration 20: fp32-level error, 1313 -> 1059 us per step at config 2); False: the
                                   # fp32 matrix pipe (configuration 17)
-    'fused_da2': True, 'fused_latent': True, 'direct_comm': True, 'cs_ride': True, 'late_dec0_dw': True, 'range_ride': True,
-    'defer_final': True, 'fused_sampler': True, 'gather_ride': True,
-    'dw_store_nt': True,          # weight gradients stored non-temporally (next read by the optimiser, a backward pass later)
-    'split_last_dw': False,       # data parallel (replicated): the last layer's dW in two launches, its first part on the wire early.
-                                  # OFF until an N > 1 A/B shows a gain: it adds a launch to the tail of the backward pass and turns
-                                  # the merged rep + enc0 message into three all-reduces (~28 us of host enqueue each); bench.py
-                                  # --tune split_last_dw=True is the A/B for the first multi-GPU box
-    'mse_colpart': True,          # the decoder's output-bias gradient from jamie_mse_cast's per-tile column sums (no fp32 d x_hat in bf16 mode)
-    'bn_panel': True,             # bf16 mode: the fp32 pre-activations / upstream gradients travel GEMM -> BatchNorm (-> BatchNorm backward)
-                                  # in panels of 16 columns (jamie_hip.h: JAMIE_PANEL): a BatchNorm strip is whole contiguous blocks per slab
     'f32_dw_group': 4,            # fp32, no gradient exchange: the large layers' dW products wait and go out `n` layers per launch
                                   # (4 layers = 2560 tiles of 128 x 128 = 5.0 rounds of 512 slots; one layer = 1.25 rounds); 1: off
 }
 
 
 def tune(**kw):
-    """Set tuning knobs (see TUNING); unknown keys raise.  Plans cached by shape are dropped."""
+    """Set tuning knobs (see TUNING); unknown keys raise.  Engines that exist keep the values they were built under."""
     for k, v in kw.items():
         if k not in TUNING:
             raise KeyError(f'unknown tuning knob {k!r}')
         TUNING[k] = v
-    _plan_f32_rows.cache_clear()
+
+
+def _int_knob(v):
+    """An integer knob's value; None when it is unset (None or '': bench.py --tune key=)."""
+    return None if v in (None, '') else int(v)
 
 
 # hyper buffer slots (device float[16]; see include/jamie_hip.h)
@@ -103,12 +93,14 @@ def _big_enough(B, shapes):
     return B >= 128 and all(N >= 256 and K >= 256 for (N, K) in shapes)
 
 
-def plan_bf16_rows(B, shapes):
-    """shapes = [(N_i, K_i)] of one forward / dX launch -> (cfg, [splitk_i]); cfg -1 = the library default."""
+def plan_bf16_rows(B, shapes, knobs=None):
+    """shapes = [(N_i, K_i)] of one forward / dX launch -> (cfg, [splitk_i]); cfg -1 = the library default.  `knobs`: the
+    tuning knobs to plan under (default: TUNING as it stands)."""
     if not _big_enough(B, shapes):
         return -1, [choose_splitk(B, N, K) for (N, K) in shapes]
-    if TUNING['bf16_rows']:
-        parts = TUNING['bf16_rows'].split(';')
+    knob = (TUNING if knobs is None else knobs)['bf16_rows']
+    if knob:
+        parts = knob.split(';')
         part = parts[0] if (all(N >= K for (N, K) in shapes) or len(parts) == 1) else parts[1]
         cfg, sks = part.split(':')
         sks = [int(v) for v in sks.split(',')]
@@ -127,8 +119,7 @@ def plan_bf16_bwd(B, shapes):
     # dX slices of ~1700 of K (config 2: (1, 1), (2, 1), (1, 1) for the three layers): re-swept at the end of round 2, when a
     # slab costs the BatchNorm launch that sums it more than it saves the GEMM (K / 1000: +5.7 us per step, unsplit K = 4000: +25,
     # profiles/r02_bwd_splitk_sweep.log)
-    per = float(TUNING['bwd_k_per_slab'])
-    return BF16_CFG_DW, [int(max(1, min(round(K / per), 4, K // 256))) for (N, K) in shapes]
+    return BF16_CFG_DW, [int(max(1, min(round(K / 1700.0), 4, K // 256))) for (N, K) in shapes]
 
 
 F32_CFG_ROWS = 17           # 128x128x32 tile on 16 waves of 32x32, barrier in mid k-step (gemm_f32.hip; 12: the barrier at the end,
@@ -146,16 +137,17 @@ F32_X3_TILE_M = 256
 F32_CFG_X3_128 = 20         # the 128 x 128 form (three LDS stages): the planner takes it where it needs fewer K slices
 
 
-def f32_cfg(kind='rows'):
-    """Tile configuration of the large fp32 launches: 'rows' (forward / dX), 'dw', 'dw_fused'."""
-    if TUNING['f32_x3']:
+def f32_cfg(knobs, kind='rows'):
+    """Tile configuration of the large fp32 launches under `knobs`: 'rows' (forward / dX), 'dw', 'dw_fused'."""
+    if knobs['f32_x3']:
         return F32_CFG_X3
     return {'rows': F32_CFG_ROWS, 'dw': F32_CFG_DW, 'dw_fused': F32_CFG_DW_FUSED}[kind]
 
 
-def _f32_fused_cfg():
-    """Tile configuration of the fp32 dW launches that also write their tiles' sums of squares (TUNING['f32_dw_cfg'] overrides)."""
-    return int(TUNING['f32_dw_cfg']) if TUNING['f32_dw_cfg'] not in (None, '') else f32_cfg('dw_fused')
+def _f32_fused_cfg(knobs):
+    """Tile configuration of the fp32 dW launches that also write their tiles' sums of squares (knob 'f32_dw_cfg' overrides)."""
+    cfg = _int_knob(knobs['f32_dw_cfg'])
+    return f32_cfg(knobs, 'dw_fused') if cfg is None else cfg
 
 
 def launch_makespan(works, n_cu=N_CU, per_cu=2, solo=0.87):
@@ -213,9 +205,11 @@ def launch_makespan(works, n_cu=N_CU, per_cu=2, solo=0.87):
     return end
 
 
-def plan_f32_rows(B, shapes):
-    """(tile configuration, K slices per problem) of an fp32 forward / dX launch; see _plan_f32_rows."""
-    return _plan_f32_rows(B, tuple(tuple(x) for x in shapes), TUNING['f32_rows'], TUNING['f32_rows_cfg'], bool(TUNING['f32_x3']))
+def plan_f32_rows(B, shapes, knobs=None):
+    """(tile configuration, K slices per problem) of an fp32 forward / dX launch; see _plan_f32_rows.  `knobs`: the tuning knobs to
+    plan under (default: TUNING as it stands)."""
+    knobs = TUNING if knobs is None else knobs
+    return _plan_f32_rows(B, tuple(tuple(x) for x in shapes), knobs['f32_rows'], _int_knob(knobs['f32_rows_cfg']), bool(knobs['f32_x3']))
 
 
 @functools.lru_cache(maxsize=256)
@@ -246,8 +240,8 @@ def _plan_f32_rows(B, shapes, _knob, _tile=None, _x3=False):
         kinds = [(F32_CFG_X3, F32_X3_TILE_M, 1.9, 4.0, 1, 1.0), (F32_CFG_X3_128, 128, 1.15, 6.0, 1, 1.0)]
     else:
         kinds = [(F32_CFG_ROWS, 128, 2.05, 3.0, 2, 0.87)]
-    if _tile not in (None, ''):
-        kinds = [k for k in kinds if k[0] == int(_tile)] or [(int(_tile),) + kinds[0][1:]]
+    if _tile is not None:
+        kinds = [k for k in kinds if k[0] == _tile] or [(_tile,) + kinds[0][1:]]
     best = None
     for cfg, bm, kstep_us, overhead, per_cu, solo in kinds:
         tiles = [math.ceil(B / bm) * math.ceil(N / 128) for (N, K) in shapes]
@@ -305,11 +299,11 @@ class TrainEngine:
             raise ValueError("dist_method must be 'euclidean' or 'cosine' (jamie.py:483-502)")
         self.loss_weights = [1., 1., 1., 1.] if loss_weights is None else [float(w) for w in loss_weights]
         assert len(self.loss_weights) == 4, f'There are 4 losses and {len(self.loss_weights)} weights'
+        # the tuning knobs as they stand now: buffers are laid out from them here and the launches are chosen from them in every
+        # step, so the engine keeps this copy whatever tune() is given later
+        self.knobs = dict(TUNING)
         f32 = dict(device=self.dev, dtype=torch.float32)
         n = model.layout.total
-        # the streams clip + Adam walks in lock step (p, m, v, g, the bf16 weight copy) start 4 KB apart modulo the allocator's
-        # 2 MB alignment: 211 instead of 215-220 us stand-alone (tools/bench_adam_offsets.py, profiles/r02_adam_buffer_placement.log)
-        self._stagger = 4096 if TUNING['stagger'] else 0
         self.exp_avg = self._flat_alloc(n, torch.float32, 1)
         self.exp_avg_sq = self._flat_alloc(n, torch.float32, 2)
         self.grad = self._flat_alloc(n, torch.float32, 3)
@@ -340,20 +334,17 @@ class TrainEngine:
         # the heads / dcomb slab counts must agree between the modalities (one latent launch reads both)
         sk_head = min(choose_splitk(B, 2 * L, d) for d in self.dims)
         sk_dcomb = min(choose_splitk(B, L, d) for d in self.dims)
-        if TUNING['sk_skinny']:
-            sk_head = sk_dcomb = int(TUNING['sk_skinny'])
+        # (N, K) of the d -> 2d and the 2d -> d products, per modality
+        up, down = [(2 * d, d) for d in self.dims], [(d, 2 * d) for d in self.dims]
         # bf16: tile configuration of every large launch + per-modality slab counts (plan_bf16_*)
         self.gcfg, plan_sk = {}, {}
+        self.skinny_tr = False
         if self.bf16:
-            grouped = 2 * self.M <= nv.MAX_GEMM_GROUP
-            for key, shp, bwd in (('enc0', [(2 * d, d) for d in self.dims], False),
-                                  ('enc1', [(d, 2 * d) for d in self.dims], False),
-                                  ('dec1', [(2 * d, d) for d in self.dims], False),
-                                  ('dec2', [(d, 2 * d) for d in self.dims], False),
-                                  ('d_e2', [(2 * d, d) for d in self.dims], True),
-                                  ('d_e1', [(d, 2 * d) for d in self.dims], True),
-                                  ('d_a1', [(2 * d, d) for d in self.dims], True)):
-                self.gcfg[key], plan_sk[key] = (plan_bf16_bwd if (bwd and grouped) else plan_bf16_rows)(B, shp)
+            for key, shp in (('enc0', up), ('enc1', down), ('dec1', up), ('dec2', down)):
+                self.gcfg[key], plan_sk[key] = plan_bf16_rows(B, shp, self.knobs)
+            for key, shp in (('d_e2', up), ('d_e1', down), ('d_a1', up)):       # (dX: grouped with the layer's dW where they fit)
+                self.gcfg[key], plan_sk[key] = (plan_bf16_bwd(B, shp) if 2 * self.M <= nv.MAX_GEMM_GROUP else
+                                                plan_bf16_rows(B, shp, self.knobs))
             self.gcfg['dw'] = BF16_CFG_DW if _big_enough(B, [(d, d) for d in self.dims]) else -1
             # the skinny head / latent backward launches go through the 128 x 128 k-row-major kernel as well: the same speed as
             # the 64 x 64 kernel on transposed copies (profiles/r02_ab_skinny_tr.log), and with no transposed weight copy left
@@ -368,12 +359,9 @@ class TrainEngine:
         # split too and its MSE / gradient come from jamie_mse_cast (a fused epilogue needs an unsplit K: 126 us)
         self.fcfg = {}
         if not self.bf16:
-            dx_nn = [] if not TUNING['f32_dx_plan'] else \
-                [('d_e2', [(2 * d, d) for d in self.dims]), ('d_a1', [(2 * d, d) for d in self.dims])]
-            for key, shp in [('enc0', [(2 * d, d) for d in self.dims]), ('enc1', [(d, 2 * d) for d in self.dims]),
-                             ('dec1', [(2 * d, d) for d in self.dims]), ('dec2', [(d, 2 * d) for d in self.dims]),
-                             ('d_e1', [(d, 2 * d) for d in self.dims])] + dx_nn:
-                cfg, sks = plan_f32_rows(B, shp)
+            dx_nn = [('d_e2', up), ('d_a1', up)] if self.knobs['f32_dx_plan'] else []
+            for key, shp in [('enc0', up), ('enc1', down), ('dec1', up), ('dec2', down), ('d_e1', down)] + dx_nn:
+                cfg, sks = plan_f32_rows(B, shp, self.knobs)
                 if cfg >= 0:
                     self.fcfg[key] = cfg
                     plan_sk[key] = sks
@@ -386,7 +374,7 @@ class TrainEngine:
         # activations / gradients that leave a BatchNorm launch are bf16 row-major as before.  Which layers take it is decided per
         # step (_set_panels): a layer's buffers are in panels only when BOTH its forward and its backward producer can write them.
         self.PANEL = int(nv.load().jamie_panel_width())
-        self.panel = bool(self.bf16 and self.fuse_bf16 and TUNING['bn_panel'] and all(d % 4 == 0 for d in self.dims)
+        self.panel = bool(self.bf16 and self.fuse_bf16 and all(d % 4 == 0 for d in self.dims)
                           and all(self.gcfg.get(k, -1) in BF16_TILE for k in ('enc0', 'enc1', 'dec1', 'd_e2', 'd_e1', 'd_a1')))
         self._pan = {'bn0': False, 'bn1': False, 'bn2': False, 'bn3': False}
         self.need_T = set()
@@ -448,7 +436,6 @@ class TrainEngine:
             self.wbf = model.layout.views(self.wbf_flat)
             # dX = dy W: the large-tile kernel reads W [out, in] as stored (b_tr: [k][n] LDS image, transposed fragment
             # reads), so only the layers whose backward launch does not take that kernel keep a transposed copy
-            self.wT = {}
             for i, d in enumerate(self.dims):
                 for lin, key in (('enc1', 'd_a1'), ('head', 'd_a2'), ('dec0', 'd_comb'), ('dec1', 'd_e1'), ('dec2', 'd_e2')):
                     if dx_from_weights and self.gcfg.get(key, -1) in BF16_TILE:
@@ -464,47 +451,27 @@ class TrainEngine:
         big = {'dec2': 'd_e2', 'dec1': 'd_e1', 'enc1': 'd_a1', 'enc0': 'dw'}
         # (the skinny head / latent layers' dW take the large tile too: their sums of squares come from the epilogue as well -- at
         #  L = 64 those two matrices alone are more range chunks than the range-norm launch carries)
-        skinny_lins = ('head', 'dec0') if (self.bf16 and getattr(self, 'skinny_tr', False)) else ()
+        skinny_lins = ('head', 'dec0') if self.skinny_tr else ()
         # (fp32 mode: the TN dW launches of the large layers take the 128 x 128 tile then -- the same speed as the 64 x 64 one
         #  inside the step, profiles/r02_f32_dw_tile_sweep.log, and a quarter of the partial sums)
-        f32_fused = (not self.bf16 and world_size == 1 and B >= 256 and TUNING['f32_fused_norm']
+        f32_fused = (not self.bf16 and world_size == 1 and B >= 256
                      and all(min(model.p[f'm{i}.{lin}.W'].shape) >= 512 for lin in big for i in range(self.M)))
         self._f32_dw_fused = f32_fused
         if f32_fused or (self.bf16 and world_size == 1 and all(self.gcfg.get(k, -1) in BF16_TILE for k in big.values())):
-            bm_d, bn_d = nv.gemm_tile(nv.TN, 1 << 20, 1 << 20, B, _f32_fused_cfg()) if f32_fused else BF16_TILE[self.gcfg['dw']]
-            self.dw_partial, off, covered = {}, 0, []
+            bm_d, bn_d = (nv.gemm_tile(nv.TN, 1 << 20, 1 << 20, B, _f32_fused_cfg(self.knobs)) if f32_fused else
+                          BF16_TILE[self.gcfg['dw']])
+            self.dw_partial, off = {}, 0
             for lin in tuple(big) + skinny_lins:
                 for i in range(self.M):
-                    o, shp = model.layout.entries[f'm{i}.{lin}.W']
+                    shp = model.layout.entries[f'm{i}.{lin}.W'][1]
                     t = math.ceil(shp[0] / bm_d) * math.ceil(shp[1] / bn_d)
                     self.dw_partial[f'm{i}.{lin}'] = (off, t)
                     off += t
-                    covered.append((o, o + shp[0] * shp[1]))
-            covered.sort()
-            rest, pos = [], 0
-            for lo, hi in covered:
-                if lo > pos:
-                    rest.append((pos, lo - pos))
-                pos = hi
-            if n > pos:
-                rest.append((pos, n - pos))
+            rest = model.layout.gaps([k + '.W' for k in self.dw_partial])
             self.sq_ranges = nv.SqRanges(rest)
             # the same without d sigma and the head-bias gradients: a step with the fused latent kernels defers their
             # finalisation to the range-norm launch's extra workgroup, which also adds their squares (optimizer_step)
-            cut = [model.layout.entries['sigma']] + [model.layout.entries[f'm{i}.head.b'] for i in range(self.M)]
-            cut = sorted((o, o + (int(np.prod(shp)) + 3) // 4 * 4) for o, shp in cut)     # (whole 4-aligned slots: the padding is zero)
-            rest2 = []
-            for lo, ln in rest:
-                hi = lo + ln
-                for c0, c1 in cut:
-                    if c0 >= hi or c1 <= lo:
-                        continue
-                    if c0 > lo:
-                        rest2.append((lo, c0 - lo))
-                    lo = max(lo, c1)
-                if hi > lo:
-                    rest2.append((lo, hi - lo))
-            self.sq_ranges_nofin = nv.SqRanges(rest2)
+            self.sq_ranges_nofin = nv.SqRanges(model.layout.without_final_slots(rest))
             if off + self.sq_ranges.blocks + 2 <= nv.load().jamie_max_norm_partials() and self.sq_ranges.blocks <= 128:
                 self.fused_norm = True
                 self.n_dw_partials = off
@@ -752,9 +719,11 @@ class TrainEngine:
         return float(t.mean())
 
     def _flat_alloc(self, n, dtype, slot):
-        """A zeroed flat buffer of `n` elements that starts `slot * self._stagger` bytes into its allocation."""
+        """A zeroed flat buffer of `n` elements that starts `slot` * 4 KB into its allocation: the streams clip + Adam walks in lock
+        step (p, m, v, g, the bf16 weight copy) start 4 KB apart modulo the allocator's 2 MB alignment: 211 instead of 215-220 us
+        stand-alone (tools/bench_adam_offsets.py, profiles/r02_adam_buffer_placement.log)."""
         es = 4 if dtype == torch.float32 else 2
-        off = slot * self._stagger // es
+        off = slot * 4096 // es
         return torch.zeros(n + off, device=self.dev, dtype=dtype)[off:]
 
     def _slabs(self, S, N):
@@ -852,8 +821,8 @@ class TrainEngine:
         and more loads in flight: no better); fp32 1512 -> 1551 us (those products are bound by the matrix pipe, not by their first
         touch of the weights, and the riders delay the BatchNorm launch): bf16 mode only.  The saved activations on top of the
         weights: 631.9 against 628.3 us with the weights alone (632.6 without): the extra ranges stretch the BatchNorm launches by
-        what the next launches gain.  TUNING['prefetch'] = 0: off."""
-        if str(TUNING['prefetch']) == '0' or self.pipeline or not self.bf16:
+        what the next launches gain."""
+        if self.pipeline or not self.bf16:
             return None
         if self._zs is not None:
             return None           # (sharded optimiser: those weights are ARRIVING by all-gather; a rider would read what RCCL writes)
@@ -934,37 +903,33 @@ class TrainEngine:
         self._launch((label, 'enc0_gemm') if lin == 'enc0' else label,
                      (lambda: nv.gemm_bf16(probs, cfg)) if self.bf16 else (lambda: nv.gemm(probs, nv.NT, fcfg)))
 
+    def _dx_problem(self, i, dy_key, lin, out_key, sk_key):
+        """dx[B, in_f] (slabs) = dy[B, out_f] W of modality `i`."""
+        w = self.ws[i]
+        out = w[out_key]
+        nout, nin = self.m.p[f'm{i}.{lin}.W'].shape
+        sk = dict(splitk=w['sk'][sk_key], slab_stride=out.stride(0))
+        if not self.bf16:
+            return nv.gemm_problem(w[dy_key], self.m.p[f'm{i}.{lin}.W'], out, self.B, nin, nout, nout, nin, nin, **sk)
+        sk['c_panel'] = self._paneled(out_key, self.gcfg.get(sk_key, -1))
+        if f'm{i}.{lin}' not in self.wT:      # dx = dy W on W [out, in] as stored (b_tr): no transposed copy
+            return nv.gemm_problem(w[dy_key + '_bf'], self.wbf[f'm{i}.{lin}.W'], out, self.B, nin, nout, nout, nin, nin, b_tr=True, **sk)
+        # dx = dy W  ==  dy (W^T)^T with the K-contiguous transposed copy (skinny layers)
+        return nv.gemm_problem(w[dy_key + '_bf'], self.wT[f'm{i}.{lin}'], out, self.B, nin, nout, nout, nout, nin, **sk)
+
     def _dx_gemm(self, dy_key, lin, out_key, sk_key):
-        """dx[B, in_f] (slabs) = dy[B, out_f] W."""
-        probs = []
-        for i, d in enumerate(self.dims):
-            w, P = self.ws[i], self.m.p
-            dy, W, out = w[dy_key], P[f'm{i}.{lin}.W'], w[out_key]
-            nout, nin = W.shape
-            if self.bf16 and f'm{i}.{lin}' not in self.wT:      # dx = dy W on W [out, in] as stored (b_tr)
-                probs.append(nv.gemm_problem(w[dy_key + '_bf'], self.wbf[f'm{i}.{lin}.W'], out, self.B, nin, nout,
-                                             nout, nin, nin, splitk=w['sk'][sk_key], slab_stride=out.stride(0), b_tr=True,
-                                             c_panel=self._paneled(out_key, self.gcfg.get(sk_key, -1))))
-            elif self.bf16:   # dx = dy W  ==  dy (W^T)^T with the K-contiguous transposed copy (skinny layers)
-                probs.append(nv.gemm_problem(w[dy_key + '_bf'], self.wT[f'm{i}.{lin}'], out, self.B, nin, nout,
-                                             nout, nout, nin, splitk=w['sk'][sk_key], slab_stride=out.stride(0),
-                                             c_panel=self._paneled(out_key, self.gcfg.get(sk_key, -1))))
-            else:
-                probs.append(nv.gemm_problem(dy, W, out, self.B, nin, nout, nout, nin, nin,
-                                             splitk=w['sk'][sk_key], slab_stride=out.stride(0)))
+        probs = [self._dx_problem(i, dy_key, lin, out_key, sk_key) for i in range(self.M)]
         if self.bf16:
             nv.gemm_bf16(probs, self.gcfg.get(sk_key, -1))
         else:
             cfg = self.fcfg.get(sk_key, -1)
-            if cfg < 0 and TUNING['f32_dx_cfg'] is not None and sk_key in ('d_e2', 'd_a1'):
-                cfg = int(TUNING['f32_dx_cfg'])
+            if cfg < 0 and self.knobs['f32_dx_cfg'] is not None and sk_key in ('d_e2', 'd_a1'):
+                cfg = int(self.knobs['f32_dx_cfg'])
             nv.gemm(probs, nv.NN, cfg)
 
-    def _dw_problems(self, dy_key, a_key, lin, only=None):
+    def _dw_problems(self, dy_key, a_key, lin):
         probs = []
         for i, d in enumerate(self.dims):
-            if only is not None and i not in only:
-                continue
             w = self.ws[i]
             dy, a, dW = w[dy_key], w[a_key], self.g[f'm{i}.{lin}.W']
             nout, nin = dW.shape
@@ -972,13 +937,13 @@ class TrainEngine:
                 probs.append(self._dw_problem(i, dy_key, a_key, lin))
             else:
                 probs.append(nv.gemm_problem(dy, a, dW, nout, nin, self.B, nout, nin, nin, accumulate=self.accumulate,
-                                             store_nt=bool(TUNING['dw_store_nt']), partial=self._dw_partial(i, lin)))
+                                             store_nt=True, partial=self._dw_partial(i, lin)))
         return probs
 
-    def _dw_gemm(self, dy_key, a_key, lin, extra=None, ranges=None, only=None):
+    def _dw_gemm(self, dy_key, a_key, lin, extra=None, ranges=None):
         """dW[out_f, in_f] = dy[B, out_f]^T a[B, in_f] into the flat gradient buffer.  `extra` = [(dy_key, a_key, lin)] of
         skinny layers whose dW rides in the same launch; `ranges` (bf16 large-tile launch only): the range-norm work rides too."""
-        probs = self._dw_problems(dy_key, a_key, lin, only)
+        probs = self._dw_problems(dy_key, a_key, lin)
         for ex in (extra or []):
             # (fp32: a skinny layer does not ride in a bf16x3 launch -- its product would then depend on which launch carried it;
             #  it keeps the fp32 pipe and a launch of its own, as in the grouped order of _flush_dw)
@@ -994,18 +959,18 @@ class TrainEngine:
             nv.gemm(probs, nv.TN, self._f32_dw_cfg(lin))
 
     def _flush_dw(self, last):
-        """fp32: the large layers' dW products that waited (+ `last`, the first layer's), TUNING['f32_dw_group'] layers per launch,
+        """fp32: the large layers' dW products that waited (+ `last`, the first layer's), knob 'f32_dw_group' layers per launch,
         the latest gradients first.  One layer is 640 tiles of 128 x 128 at config 2 = 1.25 rounds of the chip's 512 slots (half
         the chip idles through the second round); four layers are 5.0 rounds."""
         todo = ([last] if last else []) + self._dw_wait[::-1]
         small, self._dw_wait, self._dw_small = self._dw_small, None, []
-        per = max(1, min(int(TUNING['f32_dw_group']), nv.MAX_GEMM_GROUP_F32 // self.M))
+        per = max(1, min(int(self.knobs['f32_dw_group']), nv.MAX_GEMM_GROUP_F32 // self.M))
         while todo:
             chunk, todo = todo[:per], todo[per:]
             probs = []
             for dy_key, a_key, lin in chunk:
                 probs += self._dw_problems(dy_key, a_key, lin)
-            nv.gemm(probs, nv.TN, _f32_fused_cfg())
+            nv.gemm(probs, nv.TN, _f32_fused_cfg(self.knobs))
         # the skinny layers' dW (decoder layer 0, heads: 0.3 GFLOP but 16 dependent k-steps, 19 us) keep a launch of their own: as 48
         # more 128 x 128 tiles of the grouped launch, first or last in its grid, they cost 9-12 us more (the launch is exactly 10 tiles
         # per CU without them; profiles/r04_ab_f32_skinny_dw_in_grouped_launch_rejected.log)
@@ -1014,17 +979,17 @@ class TrainEngine:
 
     def _f32_dw_cfg(self, lin):
         """fp32 dW launch (TN, K = batch): tile configuration (-1: the library's 64 x 64 default)."""
-        env = TUNING['f32_dw_cfg']
-        big = self.B >= 256 and all(min(self.m.p[f'm{i}.{lin}.W'].shape) >= 512 for i in range(self.M))
-        if big and self._f32_dw_fused:
-            return _f32_fused_cfg()           # (the partial sums are laid out for this tile)
-        small = TUNING['f32_dw_small_cfg']
-        return (int(env) if env not in (None, '') else f32_cfg('dw')) if big else (int(small) if small not in (None, '') else -1)
+        if not (self.B >= 256 and all(min(self.m.p[f'm{i}.{lin}.W'].shape) >= 512 for i in range(self.M))):
+            return -1
+        if self._f32_dw_fused:
+            return _f32_fused_cfg(self.knobs)           # (the partial sums are laid out for this tile)
+        cfg = _int_knob(self.knobs['f32_dw_cfg'])
+        return f32_cfg(self.knobs, 'dw') if cfg is None else cfg
 
     def _dw_cfg(self, lin):
         """Tile configuration of the dW launch of layer `lin` (-1: the library default for small / skinny problems)."""
         big = all(min(self.m.p[f'm{i}.{lin}.W'].shape) >= 256 for i in range(self.M))
-        if getattr(self, 'skinny_tr', False) and lin in ('head', 'dec0'):
+        if self.skinny_tr and lin in ('head', 'dec0'):
             big = True
         return self.gcfg.get('dw', -1) if big else -1
 
@@ -1041,11 +1006,11 @@ class TrainEngine:
         if self._dw_tr(lin):      # dy [B, out], a [B, in] row-major as produced: no transposed copies
             if self._direct_now:      # data parallel, bf16 messages: straight into the exchange buffer (no fp32 copy, no cast pass)
                 return nv.gemm_problem(w[dy_key + '_bf'], w[a_key + '_bf'], self._direct['views'][f'm{i}.{lin}.W'], nout, nin,
-                                       self.B, nout, nin, nin, a_tr=True, b_tr=True, store_nt=bool(TUNING['dw_store_nt']), c_bf16=True)
+                                       self.B, nout, nin, nin, a_tr=True, b_tr=True, store_nt=True, c_bf16=True)
             g16 = self._g16_now and f'm{i}.{lin}' in self.dw_partial
             return nv.gemm_problem(w[dy_key + '_bf'], w[a_key + '_bf'], self.g16[f'm{i}.{lin}.W'] if g16 else dW, nout, nin,
                                    self.B, nout, nin, nin, accumulate=self.accumulate, partial=self._dw_partial(i, lin),
-                                   a_tr=True, b_tr=True, store_nt=bool(TUNING['dw_store_nt']), c_bf16=g16)
+                                   a_tr=True, b_tr=True, store_nt=True, c_bf16=g16)
         # (dy^T) (a^T)^T on the [features, B] copies, K (= batch) contiguous
         return nv.gemm_problem(w[dy_key + '_T'], w[a_key + '_T'], dW, nout, nin, self.B, self.B, self.B, nin,
                                accumulate=self.accumulate, partial=self._dw_partial(i, lin), store_nt=True)
@@ -1061,7 +1026,7 @@ class TrainEngine:
         """dW (into the gradient buffer) and dX (slabs) of one Linear layer.  In bf16 mode both are the same
         K-contiguous NT product, so the four problems (2 modalities x {dW, dX}) go out as ONE grouped launch.
         `extra` = [(dy_key, a_key, lin)]: the dW problems of skinny layers ride in the same launch."""
-        if not self.bf16 and self._dw_wait is not None and self._f32_dw_cfg(lin) == _f32_fused_cfg():
+        if not self.bf16 and self._dw_wait is not None and self._f32_dw_cfg(lin) == _f32_fused_cfg(self.knobs):
             # fp32: the weight gradient is not on the critical chain -- it waits for the end of the pass (_flush_dw)
             self._dw_wait.append((dy_key, a_key, lin))
             self._dw_small += list(extra or [])
@@ -1084,20 +1049,8 @@ class TrainEngine:
         # grid so that the short dW tiles fill in behind them (in-kernel stamps: the launch ends 4-5 us earlier).
         # (fp32's order -- dX launches alone, every dW tile in one last launch -- costs bf16 +33 us per step: here the dW tiles ARE
         #  the filler of the dX launches, profiles/r04_ab_bf16_dw_all_in_last_launch_rejected.log)
-        probs = []
-        for i, d in enumerate(self.dims):
-            w = self.ws[i]
-            nout, nin = self.g[f'm{i}.{lin}.W'].shape
-            if f'm{i}.{lin}' not in self.wT:                    # W [out, in] as stored (b_tr): no transposed copy
-                probs.append(nv.gemm_problem(w[dy_key + '_bf'], self.wbf[f'm{i}.{lin}.W'], w[out_key], self.B, nin, nout,
-                                             nout, nin, nin, splitk=w['sk'][sk_key], slab_stride=w[out_key].stride(0), b_tr=True,
-                                             c_panel=self._paneled(out_key, self.gcfg.get(sk_key, -1))))
-            else:
-                probs.append(nv.gemm_problem(w[dy_key + '_bf'], self.wT[f'm{i}.{lin}'], w[out_key], self.B, nin, nout,
-                                             nout, nout, nin, splitk=w['sk'][sk_key], slab_stride=w[out_key].stride(0),
-                                             c_panel=self._paneled(out_key, self.gcfg.get(sk_key, -1))))
-        for i, d in enumerate(self.dims):
-            probs.append(self._dw_problem(i, dy_key, a_key, lin))
+        probs = [self._dx_problem(i, dy_key, lin, out_key, sk_key) for i in range(self.M)]
+        probs += [self._dw_problem(i, dy_key, a_key, lin) for i in range(self.M)]
         for ex in riding:
             probs += self._dw_problems(*ex)
         nv.gemm_bf16(probs, self.gcfg.get(sk_key, -1), ranges)
@@ -1146,11 +1099,9 @@ class TrainEngine:
         """The heads' input gradient d a2 = d(mu | logvar) W_head as extra workgroups of the fused latent backward launch
         (exact fp32, K = 2L) instead of a GEMM launch; the heads' dW then rides in the next layer's launch."""
         return (all(d % 4 == 0 for d in self.dims) and all(w['sk']['d_a2'] == 1 for w in self.ws)
-                and (not self.bf16 or self.skinny_tr) and TUNING['fused_da2'])
+                and (not self.bf16 or self.skinny_tr))
 
     def _fused_latent(self, corr, Fblk):
-        if self.M == 2 and not TUNING['fused_latent']:      # (A/B: the general kernels)
-            return False
         return corr is None and Fblk is None and not self.cosine and self.L <= 128
 
     def _latent_desc(self, corr, Fblk, noise, fused=False):
@@ -1212,12 +1163,8 @@ class TrainEngine:
             if name not in self.m.layout.regions:      # (heads / decoder layer 0: their gradients travel with `rep`)
                 return
             lo, hi = self.m.layout.regions[name]
-            if self._direct_now:
-                fn = lambda: ar.region_done(self.grad, lo, hi, precast=True)   # noqa: E731
-            else:
-                fn = lambda: ar.region_done(self.grad, lo, hi)   # noqa: E731
-            nv.record_callable(fn)
-            fn()
+            precast = self._direct_now
+            self._both(lambda: ar.region_done(self.grad, lo, hi, precast=precast))
 
     def pad_cells(self, data):
         """[N, d_i] cell matrices -> [N, pdims_i] (zero columns appended) when the model is padded; else unchanged."""
@@ -1322,15 +1269,14 @@ class TrainEngine:
             for i, d in enumerate(self.dims):
                 w = self.ws[i]
                 rd = self.rdims[i]
-                cp = bool(TUNING['mse_colpart'])
-                probs.append(nv.mse_problem(w['xh'], w['x'], None if (self.bf16 and cp) else w['dxhat'], w.get('dxhat_bf'),
+                probs.append(nv.mse_problem(w['xh'], w['x'], None if self.bf16 else w['dxhat'], w.get('dxhat_bf'),
                                             w['dxhat_T'] if 'dxhat' in self.need_T else None,
                                             partial=self.rec_partials[off:off + self.rec_tiles[i]],
                                             scale=self.loss_weights[1] * 2.0 / (B * rd), pscale=1.0 / (B * rd),
-                                            colpart=w['dxhat_cp'] if cp else None))
+                                            colpart=w['dxhat_cp']))
                 off += self.rec_tiles[i]
             nv.mse_cast(probs)
-            self._dxhat_cs = 'dxhat_cp' if TUNING['mse_colpart'] else 'dxhat'
+            self._dxhat_cs = 'dxhat_cp'
             return lat
         probs, off = [], 0
         for i, d in enumerate(self.dims):                                 # x_hat GEMM + fused MSE
@@ -1348,17 +1294,21 @@ class TrainEngine:
         self._cast('dxhat')
         return lat
 
+    def _reduced_in_bf16(self, allreduce):
+        """bf16 messages: the exchange keeps the reduced gradient in its bf16 buffer (norm and Adam read it there)."""
+        return (getattr(allreduce, 'comm_dtype', None) == torch.bfloat16 and self.grad.is_cuda
+                and (getattr(allreduce, 'world', 1) > 1 or getattr(allreduce, 'single', False)))
+
     def _direct_setup(self, allreduce):
         """Data parallel with bf16 messages: every producer writes its gradients into the exchange's bf16 buffer itself -- the
         dW epilogues store bf16 there (c_bf16; no fp32 copy of the weight gradients), the few KB of bias / BatchNorm / sigma
         gradients are copied by a rider of the last GEMM launch (range_norm.h with the message buffer as the
         bf16 copy; no step-counter increment) -- so the fp32 -> bf16 cast pass over the 161 MB gradient (a second stream beside
         the backward GEMMs, two events per region) does not exist.  Returns None where the path does not apply."""
-        ok = (allreduce is not None and hasattr(allreduce, 'message_buffer') and getattr(allreduce, 'comm_dtype', None) == torch.bfloat16
-              and (getattr(allreduce, 'world', 1) > 1 or getattr(allreduce, 'single', False)) and self.bf16 and self.grad.is_cuda and not self.accumulate
+        ok = (self._reduced_in_bf16(allreduce) and hasattr(allreduce, 'message_buffer') and self.bf16 and not self.accumulate
               and self.gcfg.get('dw', -1) == BF16_CFG_DW and self.skinny_tr and 3 * self.M <= nv.MAX_GEMM_GROUP
               and all(self.gcfg.get(k, -1) == BF16_CFG_DW for k in ('d_e2', 'd_e1', 'd_a1'))
-              and self._fused_latent(None, None) and self._fuse_da2() and TUNING['direct_comm'])
+              and self._fused_latent(None, None) and self._fuse_da2())
         if not ok:
             return None
         comm = allreduce.message_buffer(self.grad)
@@ -1367,30 +1317,10 @@ class TrainEngine:
             # the small tensors all live in region `rep`, which is announced last (with enc0): ONE rider, on the enc0 dW launch,
             # copies what no GEMM epilogue writes there (everything but the two skinny weight matrices per modality)
             lo, hi = lay.regions['rep']
-            big = sorted((o, o + int(np.prod(shp))) for k, (o, shp) in lay.entries.items() if k.endswith('.W') and lo <= o < hi)
-            rest, pos = [], lo
-            for a, b in big:
-                if a > pos:
-                    rest.append((pos, a - pos))
-                pos = b
-            if hi > pos:
-                rest.append((pos, hi - pos))
+            rest = lay.gaps([k for k, (o, _) in lay.entries.items() if k.endswith('.W') and lo <= o < hi], lo, hi)
             # the latent block's finalisation (d sigma, the head-bias gradients: fp32 and bf16 copies) is deferred to that same
             # rider: those slots are cut out of its ranges
-            cut = sorted((o, o + (int(np.prod(shp)) + 3) // 4 * 4) for o, shp in
-                         [lay.entries['sigma']] + [lay.entries[f'm{i}.head.b'] for i in range(self.M)])
-            small = []
-            for lo_, ln_ in rest:
-                hi_ = lo_ + ln_
-                for c0, c1 in cut:
-                    if c0 >= hi_ or c1 <= lo_:
-                        continue
-                    if c0 > lo_:
-                        small.append((lo_, c0 - lo_))
-                    lo_ = max(lo_, c1)
-                if hi_ > lo_:
-                    small.append((lo_, hi_ - lo_))
-            rg = nv.SqRanges(small)
+            rg = nv.SqRanges(lay.without_final_slots(rest))
             rides = {'enc0': (self.grad, comm, rg, torch.zeros(rg.blocks + 1, device=self.dev, dtype=torch.float32), None, None)}
             self._direct = {'comm': comm, 'views': lay.views(comm), 'rides': rides}
         return self._direct
@@ -1398,7 +1328,9 @@ class TrainEngine:
     def _backward(self, lat, noise, allreduce, sample=None):
         B, L = self.B, self.L
         acc = self.accumulate
-        direct = self._direct_setup(allreduce) if isinstance(lat, nv.LatentM) and lat.da2[0] else None
+        # the heads' input gradient comes out of the latent backward launch (fused kernels)?
+        fused_tail = isinstance(lat, nv.LatentM) and bool(lat.da2[0])
+        direct = self._direct_setup(allreduce) if fused_tail else None
         self._direct_now = direct is not None
         dr = dict(direct['rides']) if direct else {}
         if direct:                     # the finaliser rides with the small pieces (enc0 launch, the last of the pass)
@@ -1409,7 +1341,7 @@ class TrainEngine:
             self.refresh_weights_bf16(transposes_only=True)
             self._wT_stale = False
         self._fuse_now = self.fused_norm and allreduce is None      # a reduced gradient needs its norm taken afterwards
-        self._dw_wait = [] if (not self.bf16 and allreduce is None and int(TUNING['f32_dw_group']) > 1
+        self._dw_wait = [] if (not self.bf16 and allreduce is None and int(self.knobs['f32_dw_group']) > 1
                                and self.M <= nv.MAX_GEMM_GROUP_F32) else None
         self._dw_small = []
         self._g16_now = self.grad_bf16 and self._fuse_now and not self.accumulate
@@ -1421,28 +1353,23 @@ class TrainEngine:
             self.grad16, self.g16, self._g16_last = direct['comm'], direct['views'], True
         # the decoder's output-bias gradient (column sums of d x_hat) rides in the first BatchNorm-backward launch as extra
         # workgroups (47 short ones beside 375 long ones) instead of being a launch of its own at the head of the backward
-        # pass (with a gradient exchange too: the biases live in region `rep`, which is announced last)
-        ride = bool(TUNING['cs_ride'])
-        # (column sums of d x_hat: of the per-tile sums jamie_mse_cast left, where that launch made d x_hat; of d x_hat itself otherwise)
+        # pass (with a gradient exchange too: the biases live in region `rep`, which is announced last): the column sums of the
+        # per-tile sums jamie_mse_cast left, where that launch made d x_hat; of d x_hat itself otherwise
         cs_items = [(self.ws[i][self._dxhat_cs], self.g[f'm{i}.dec2.b']) for i in range(len(self.dims))]
-        if not ride:
-            nv.colsum_group(cs_items, acc)
         self._bwd_gemms('dxhat', 'dec2', 'e2', 'de2', 'd_e2', ranges=dr.get('dec2'))
         self._region(allreduce, 'dec2')
         self._bn_bwd('bn3', 'de2', 'g2', 'dec1', 13, noise, 'dec_masks', 1,
-                     colsums=nv.colsum_problems(cs_items, acc) if ride else None,
+                     colsums=nv.colsum_problems(cs_items, acc),
                      prefetch=('dec1',))   # de2[0] <- dg2p   (next: dX / dW of dec1, then BatchNorm backward on g1)
         self._cast('de2')
         self._bwd_gemms('de2', 'dec1', 'e1', 'de1', 'd_e1', ranges=dr.get('dec1'))
         self._region(allreduce, 'dec1')
         self._bn_bwd('bn2', 'de1', 'g1', 'dec0', 12, noise, 'dec_masks', 0)   # de1[0] <- dg1p
         self._cast('de1')
-        # the heads' input gradient comes out of the latent backward launch (fused kernels); the dW products of the two skinny
-        # layers (decoder layer 0, heads: K = batch, the longest tiles of their launches) then ride in the next big layer's
-        # launch, and what is left here is the short d comb product alone
+        # fused tail: the dW products of the two skinny layers (decoder layer 0, heads: K = batch, the longest tiles of their
+        # launches) ride in the next big layer's launch, and what is left here is the short d comb product alone
         late_dw = []
-        fused_tail = isinstance(lat, nv.LatentM) and bool(lat.da2[0])
-        if fused_tail and (self._direct_now or TUNING['late_dec0_dw']):
+        if fused_tail:
             self._dx_gemm('de1', 'dec0', 'dcomb', 'd_comb')
             late_dw.append(('de1', 'comb', 'dec0'))
         else:
@@ -1457,7 +1384,7 @@ class TrainEngine:
         if not (isinstance(lat, nv.LatentM) and lat.colpart):                   # (fused kernels: bf16 dml + head-bias gradients done)
             self._cast('dml')
             nv.colsum_group([(self.ws[i]['dml'], self.g[f'm{i}.head.b']) for i in range(len(self.dims))], acc)
-        if isinstance(lat, nv.LatentM) and lat.da2[0]:      # d a2 came out of the latent launch: only the heads' dW is left,
+        if fused_tail:                                      # d a2 came out of the latent launch: only the heads' dW is left,
             late_dw.append(('dml', 'a2', 'head'))           # and it rides in the next layer's launch
         else:
             self._bwd_gemms('dml', 'head', 'a2', 'da2', 'd_a2')
@@ -1476,40 +1403,9 @@ class TrainEngine:
         #  events, profiles/r02_ab_range_norm_side_stream_rejected.log)
         # ... but as EXTRA workgroups of that last dW launch the range norm (and the latent finalisation) costs nothing: every
         # other gradient exists by now
-        ride = (self._fuse_now and self.bf16 and self._dw_cfg('enc0') == BF16_CFG_DW and TUNING['range_ride'])
-        # Data parallel with the replicated optimiser: this is the LAST gradient of the pass, and whatever of it is still on the wire
-        # when the pass ends is exposed in full.  The first M - 1 modalities' weight gradients (config 2: 16 of the layer's 20 MB
-        # as bf16) go out in a launch of their own and their message is issued at once; the last modality's launch carries the
-        # riders, and only its part (+ `rep`) is announced at the end.  (Reasoned, not measured: no multi-GPU box -- so it is an
-        # opt-in knob, TUNING['split_last_dw'], not the default.)
-        split = (allreduce is not None and hasattr(allreduce, 'region_done') and self._zs is None and self.M >= 2
-                 and TUNING['split_last_dw'] and not self.accumulate
-                 and (getattr(allreduce, 'world', 1) > 1 or getattr(allreduce, 'single', False)))
-        if split:
-            lo, hi = self.m.layout.regions['enc0']
-            cut = self.m.layout.entries[f'm{self.M - 1}.enc0.W'][0]
-            self._dw_gemm('da1', 'x', 'enc0', only=range(self.M - 1))
-            if self._direct_now:
-                fn = lambda: allreduce.region_done(self.grad, lo, cut, precast=True, force=True)   # noqa: E731
-            else:
-                fn = lambda: allreduce.region_done(self.grad, lo, cut, force=True)   # noqa: E731
-            nv.record_callable(fn)
-            fn()
-            self._dw_gemm('da1', 'x', 'enc0', only=[self.M - 1], ranges=dr.get('enc0'))
-            self._ranges_done = False
-            rlo, rhi = self.m.layout.regions['rep']
-            for a, b in ((cut, hi), (rlo, rhi)):
-                if self._direct_now:
-                    fn = lambda a=a, b=b: allreduce.region_done(self.grad, a, b, precast=True)   # noqa: E731
-                else:
-                    fn = lambda a=a, b=b: allreduce.region_done(self.grad, a, b)   # noqa: E731
-                nv.record_callable(fn)
-                fn()
-            self._norm_ready = self._fuse_now
-            self.m.num_batches_tracked += 1
-            return
+        ride = self._fuse_now and self.bf16 and self._dw_cfg('enc0') == BF16_CFG_DW
         if self._dw_wait is not None:
-            big_last = self._f32_dw_cfg('enc0') == _f32_fused_cfg()
+            big_last = self._f32_dw_cfg('enc0') == _f32_fused_cfg(self.knobs)
             self._flush_dw(('da1', 'x', 'enc0') if big_last else None)
             if not big_last:
                 self._dw_gemm('da1', 'x', 'enc0')
@@ -1613,8 +1509,7 @@ class TrainEngine:
         # the fused latent backward kernel leaves its finalisation (losses, d sigma, head-bias gradients) to the range-norm
         # launch that follows in this very step when that launch exists (bf16 mode, one GPU, fused gradient norm)
         defer = (self.fused_norm and self.sq_ranges_nofin.blocks <= 128 and allreduce is None and not self.accumulate
-                 and self._fused_latent(corr, Fblk)
-                 and TUNING['defer_final'])
+                 and self._fused_latent(corr, Fblk))
         lat = self._forward(corr, Fblk, noise, True)
         if defer and isinstance(lat, nv.LatentM):
             lat.defer_final = 1
@@ -1624,25 +1519,17 @@ class TrainEngine:
         if self._zs is not None:
             if allreduce is not self._zs['ex']:
                 raise nv.JamieHipError('sharded optimiser: step() must be given the exchange it was enabled with')
-            fn = lambda: allreduce.finish(copy_back=False)     # noqa: E731
-            nv.record_callable(fn)
-            fn()
+            self._both(lambda: allreduce.finish(copy_back=False))
             if after_norm is not None:
                 raise nv.JamieHipError('sharded optimiser: no side-stream batch prefetch')
             self._sharded_step(None if next_casts else sample, next_casts)
             return
         if allreduce is not None:
-            # bf16 messages: the reduced gradient stays in the exchange's bf16 buffer; norm and Adam read it there
-            in_place = (getattr(allreduce, 'comm_dtype', None) == torch.bfloat16 and self.grad.is_cuda
-                        and (getattr(allreduce, 'world', 1) > 1 or getattr(allreduce, 'single', False)))
-            if in_place:
-                fn = lambda: allreduce.finish(copy_back=False)     # noqa: E731
-            else:
-                fn = allreduce.finish if hasattr(allreduce, 'finish') else (lambda: allreduce(self.grad))
-            nv.record_callable(fn)
-            fn()
-            if in_place:
+            if self._reduced_in_bf16(allreduce):
+                self._both(lambda: allreduce.finish(copy_back=False))
                 g16 = allreduce.comm
+            else:
+                self._both(allreduce.finish if hasattr(allreduce, 'finish') else (lambda: allreduce(self.grad)))
         self.optimizer_step(g16, after_norm, None if next_casts else sample, next_casts)
 
     # ---- recorded launch plan: one foreign call per launch, no descriptor rebuilding (host cost ~3 us/launch) ----
@@ -1663,13 +1550,12 @@ class TrainEngine:
         if not prefetch:
             # the sampler of the NEXT batch rides in this step's clip + Adam launch (one extra workgroup: the same index
             # stream, no launch of its own); the first batch is drawn here, before the recording
-            fused = not self.pipeline and (replace or idx.numel() <= 2048) and TUNING['fused_sampler']
+            fused = not self.pipeline and (replace or idx.numel() <= 2048)
             # ... and where the latent backward launch can carry the sampler (fused M-modality kernels, identity
             # correspondence, no weight transposes waiting for Adam's output) the next batch's GATHER rides in clip + Adam
             # too: the batch buffers are free once the last dW product has run, and the step is then fwd + bwd + norm + Adam
             early = (fused and not self.wT and not replace and self._fused_latent(corr, None)
-                     and all(x.shape[1] % 4 == 0 and x.dtype == torch.float32 for x in data)
-                     and TUNING['gather_ride'])
+                     and all(x.shape[1] % 4 == 0 and x.dtype == torch.float32 for x in data))
             if fused:
                 nv.sample_indices(idx, n_rows, 0, replace, self.state, 200)
             if early:

@@ -123,6 +123,41 @@ class ParamLayout:
     def bn_views(self, flat):
         return {k: flat[o:o + int(np.prod(s))].view(*s) for k, (o, s) in self.bn_entries.items()}
 
+    # ---- which elements of the flat gradient a range kernel has to visit (engine.TrainEngine: clip norm, bf16 copies) ----
+    def gaps(self, covered, lo=0, hi=None):
+        """[(offset, length)] of [lo, hi) (default: the whole buffer) outside the weight matrices `covered` (entry names):
+        what no dW epilogue of those matrices writes -- the small tensors, the alignment padding, the other matrices."""
+        hi = self.total if hi is None else hi
+        out, pos = [], lo
+        for a, n in sorted((self.entries[k][0], int(np.prod(self.entries[k][1]))) for k in covered):
+            if a > pos:
+                out.append((pos, a - pos))
+            pos = a + n
+        if hi > pos:
+            out.append((pos, hi - pos))
+        return out
+
+    def final_slots(self):
+        """[(lo, hi)], ascending: the whole 4-aligned slots (the padding is zero) of sigma and the head biases, whose gradients the
+        fused latent backward pass can leave to a finalising workgroup of a later launch."""
+        return sorted((o, o + (int(np.prod(shp)) + 3) // 4 * 4)
+                      for o, shp in [self.entries['sigma']] + [self.entries[f'm{i}.head.b'] for i in range(self.M)])
+
+    def without_final_slots(self, ranges):
+        """`ranges` [(offset, length)] minus final_slots()."""
+        out = []
+        for lo, ln in ranges:
+            hi = lo + ln
+            for c0, c1 in self.final_slots():
+                if c0 >= hi or c1 <= lo:
+                    continue
+                if c0 > lo:
+                    out.append((lo, c0 - lo))
+                lo = max(lo, c1)
+            if hi > lo:
+                out.append((lo, hi - lo))
+        return out
+
     def num_parameters(self):
         """Reference count: sum_i(8d^2 + 3dL + 19d + 2L) + M; padding is not counted."""
         return sum(int(np.prod(self.real[k])) for k in self.entries)

@@ -944,6 +944,57 @@ def test_fp32_weight_gradients_grouped_at_the_end_equal_one_launch_per_layer(jam
             assert torch.equal(a, b)
 
 
+def test_an_engine_keeps_the_tuning_knobs_it_was_built_under(jam):
+    """engine.tune() after an engine exists does not reach it: its buffers were laid out from the knobs at construction, so its
+    launches are chosen from the same copy.  fp32 at the smallest shape with the fused clip norm (B = 256, every large weight's
+    shorter side 512): engine A, built under the defaults and stepped under f32_dw_group=1, issues the launches of engine B (built
+    and stepped under the defaults) and leaves the same bits; engine C, BUILT under f32_dw_group=1, issues one dW launch per layer.
+    (f32_dw_group only: its two values are bit-identical and share a buffer layout.)"""
+    from jamie_amd import _native as nv, engine
+    from jamie_amd.engine import TrainEngine
+    from jamie_amd.model import edModelVar
+    B, dims, L = 256, (512, 512), 8
+    g = torch.Generator().manual_seed(5)
+    X = [torch.randn(B, d, generator=g).cuda() for d in dims]
+
+    def build():
+        torch.manual_seed(666)
+        model = edModelVar(dims, L)
+        eng = TrainEngine(model, B, seed=3)
+        assert eng._f32_dw_fused
+        eng.set_batch(X)
+        return model, eng
+
+    def recorded_step(model, eng):
+        nv.begin_record()
+        try:
+            eng.step()
+        finally:
+            plan = nv.end_record()
+        torch.cuda.synchronize()
+        names = [fn.__name__ for fn, args in plan if args is not None and fn is not nv._SET_STREAM]
+        return names, (eng.grad.clone(), eng.norm_partials.clone(), model.flat.clone())
+
+    assert engine.TUNING['f32_dw_group'] == 4
+    a = build()
+    try:
+        engine.tune(f32_dw_group=1)
+        names_a, bits_a = recorded_step(*a)
+    finally:
+        engine.tune(f32_dw_group=4)
+    names_b, bits_b = recorded_step(*build())
+    try:
+        engine.tune(f32_dw_group=1)
+        c = build()
+    finally:
+        engine.tune(f32_dw_group=4)
+    names_c, _ = recorded_step(*c)
+    assert names_a == names_b
+    assert names_c != names_b and names_c.count('jamie_gemm_f32_cfg') > names_b.count('jamie_gemm_f32_cfg')
+    for x, y in zip(bits_a, bits_b):
+        assert torch.equal(x, y)
+
+
 @pytest.mark.parametrize('B,dims,L,p', [(64, (40, 32, 24), 8, 0.0), (256, (264, 200, 136), 16, 0.6),
                                         (96, (56, 44, 36), 10, 0.6), (64, (40, 32, 24, 20), 6, 0.0), (128, (72, 48, 40), 33, 0.6)])
 def test_three_modalities_step_vs_generalised_oracle(jam, B, dims, L, p):

@@ -97,7 +97,7 @@ def test_package_reads_no_environment_switches():
     from jamie_amd import engine
     with pytest.raises(KeyError):
         engine.tune(no_such_knob=1)
-    engine.tune(prefetch=1)
+    engine.tune(f32_dw_group=4)
 
 
 def test_ctypes_struct_sizes_match_header(lib, tmp_path):
@@ -593,3 +593,78 @@ def test_three_piece_cut_of_an_fp32_value_is_exact():
     scale = np.abs(a.astype(np.float64) * b.astype(np.float64))
     ok = scale > 0
     assert (dropped[ok] <= scale[ok] * 2.0 ** -21).all() and np.median(dropped[ok] / scale[ok]) < 2.0 ** -24
+
+
+RETIRED_KNOBS = ('cs_ride', 'range_ride', 'late_dec0_dw', 'defer_final', 'fused_sampler', 'gather_ride', 'fused_da2', 'fused_latent',
+                 'direct_comm', 'dw_store_nt', 'mse_colpart', 'bn_panel', 'stagger', 'f32_fused_norm', 'prefetch', 'sk_skinny',
+                 'bwd_k_per_slab', 'f32_dw_small_cfg', 'split_last_dw')
+
+
+def test_tuning_knobs_are_the_eight_a_test_or_tool_sets_and_an_engine_reads_its_own_copy():
+    """engine.TUNING holds the launch-plan knobs only (the switches back to the older variant of an adopted change are retired:
+    EXPERIMENTS.md), tune() of a retired key raises like any unknown key, and TrainEngine names the module-level dict exactly
+    once -- where it takes its copy at construction: no launch of an existing engine depends on a later tune()."""
+    import ast
+    import inspect
+    import io
+    import textwrap
+    import tokenize
+    from jamie_amd import engine
+    assert set(engine.TUNING) == {'bf16_rows', 'f32_rows', 'f32_rows_cfg', 'f32_dw_cfg', 'f32_dx_cfg', 'f32_dx_plan', 'f32_x3',
+                                  'f32_dw_group'}
+    before = dict(engine.TUNING)
+    for k in RETIRED_KNOBS:
+        with pytest.raises(KeyError):
+            engine.tune(**{k: 1})
+    assert engine.TUNING == before
+    src = textwrap.dedent(inspect.getsource(engine.TrainEngine))
+    tree = ast.parse(src)
+    doc_lines = set()
+    for node in ast.walk(tree):
+        if isinstance(node, (ast.ClassDef, ast.FunctionDef)) and ast.get_docstring(node) is not None:
+            d = node.body[0]
+            doc_lines.update(range(d.lineno, d.end_lineno + 1))
+    uses = [t for t in tokenize.generate_tokens(io.StringIO(src).readline)
+            if t.type == tokenize.NAME and t.string == 'TUNING' and t.start[0] not in doc_lines]
+    assert len(uses) == 1, [t.line for t in uses]
+    assert re.search(r'self\.\w+\s*=\s*dict\(TUNING\)', uses[0].line), uses[0].line
+    # a string or an attribute cannot smuggle the global in either
+    code = [t.string for t in tokenize.generate_tokens(io.StringIO(src).readline)
+            if t.type not in (tokenize.COMMENT,) and t.start[0] not in doc_lines]
+    assert sum('TUNING' in c for c in code) == 1
+
+
+LAYOUTS = (((2000, 1000), 32), ((2000, 1000, 500), 32), ((5000, 2000), 64), ((512, 512), 8), ((256, 264), 8))
+
+
+@pytest.mark.parametrize('lins,gap_elements', [(('enc0', 'enc1', 'dec1', 'dec2'), (347136, 403328, 1479168, 44544, 24064)),
+                                               (('enc0', 'enc1', 'dec1', 'dec2', 'head', 'dec0'), (59136, 67328, 135168, 19968, 11584))])
+def test_gradient_ranges_outside_the_covered_matrices_tile_the_flat_buffer(lins, gap_elements):
+    """ParamLayout.gaps / final_slots / without_final_slots (the ranges the clip-norm range kernel visits: engine.TrainEngine):
+    the covered weight matrices, the cut sigma / head-bias slots and the returned ranges tile [0, total) exactly once, in ascending
+    order, none of them empty; the element counts of the gaps before the cut are those of the loops the engine used to carry."""
+    from jamie_amd.model import ParamLayout
+    for (dims, L), want in zip(LAYOUTS, gap_elements):
+        lay = ParamLayout(dims, L)
+        covered = [f'm{i}.{lin}.W' for lin in lins for i in range(len(dims))]
+        gaps = lay.gaps(covered)
+        assert sum(n for _, n in gaps) == want, (dims, L, sum(n for _, n in gaps))
+        assert gaps == sorted(gaps) and all(n > 0 for _, n in gaps)
+        slots = lay.final_slots()
+        assert slots == sorted(slots) and len(slots) == 1 + len(dims) and all((hi - lo) % 4 == 0 and hi > lo for lo, hi in slots)
+        assert slots[0][0] == lay.entries['sigma'][0] and all(lay.entries[f'm{i}.head.b'][0] in [lo for lo, _ in slots]
+                                                              for i in range(len(dims)))
+        rest = lay.without_final_slots(gaps)
+        assert rest == sorted(rest) and all(n > 0 for _, n in rest)
+        mats = [(lay.entries[k][0], lay.entries[k][0] + int(np.prod(lay.entries[k][1]))) for k in covered]
+        pieces = sorted(mats + slots + [(o, o + n) for o, n in rest])
+        assert pieces[0][0] == 0 and pieces[-1][1] == lay.total
+        assert all(a[1] == b[0] for a, b in zip(pieces, pieces[1:])), (dims, L)
+        assert all(hi > lo for lo, hi in pieces)
+        # a sub-range of the buffer (the data-parallel rider covers region `rep` alone): the same tiling inside it
+        lo, hi = lay.regions['rep']
+        inside = [k for k in covered if lo <= lay.entries[k][0] < hi]
+        sub = lay.gaps(inside, lo, hi)
+        assert sum(n for _, n in sub) + sum(int(np.prod(lay.entries[k][1])) for k in inside) == hi - lo
+        assert all(lo <= o and o + n <= hi and n > 0 for o, n in sub)
+
