@@ -552,6 +552,28 @@ int jamie_cross_knn(const float* Q, long long Nq, const float* R, long long Nr, 
 int jamie_knn_vote(const int32_t* idx, long long Nq, int K, const int32_t* ref_codes, int n_classes, int32_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
+ * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
+ * sums in a fixed order and integer atomics only; bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` (host arithmetic only, no device needed).  which = 0: jamie_feature_stats on [N, d].  which = 1:
+ * jamie_feature_auroc on a group of d features of N cells: two uint32 key buffers [d, Npad], Npad = N rounded up to a multiple of
+ * 4096.  0 for any other `which` or N, d < 1 */
+long long jamie_imputation_workspace(long long N, int d, int which);
+/* r[f] = Pearson correlation of X[:, f] and Y[:, f], mse[f] = mean (X[:, f] - Y[:, f])^2, fp64 [d] each.  Every element is widened
+ * to fp64 and shifted by row 0's value of its feature before the sums dx, dy, dx^2, dy^2, dx dy are taken in fp64; (x - y)^2 is
+ * taken on the widened values.  r is NaN exactly where a column of X or of Y is constant.  2 <= N <= 65535 * 512 */
+int jamie_feature_stats(const float* X, const float* Y, long long N, int d, double* r, double* mse, void* ws, long long ws_bytes,
+                        void* stream);
+/* For the features f in [f0, f0 + dg), 1 <= dg <= 32768: label Y[i, f] > thr[f] (strict; thr fp32 [d] on the device), score X[i, f].
+ * n_pos[f] = number of positives, U2[f] = sum over the positives p of (2 #{negatives < p} + #{negatives == p}): twice the
+ * Mann-Whitney U with ties at 1/2, an exact integer; AUROC = U2 / (2 n_pos n_neg).  int64 [d] each, entries outside the group
+ * untouched.  Scores compare as floats (-0.0 == +0.0).  last_stage = 4; 1 .. 3 stop after the key pass, the chunk sort, the merge
+ * passes (for timing the stages: U2 is then not formed) */
+int jamie_feature_auroc(const float* X, const float* Y, long long N, int d, const float* thr, int f0, int dg, long long* n_pos,
+                        long long* U2, void* ws, long long ws_bytes, int last_stage, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

@@ -217,6 +217,11 @@ EXPORTS = {
     'jamie_cross_knn': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_knn_vote': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                      C.c_void_p]),
+    'jamie_feature_auroc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -742,6 +747,22 @@ def cross_knn(Q, R, K, idx, dist, ws):
 
 def knn_vote(idx, ref_codes, n_classes, pred):
     _call('jamie_knn_vote', ptr(idx), idx.shape[0], idx.shape[1], ptr(ref_codes), int(n_classes), ptr(pred), _stream())
+
+
+# ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----
+def imputation_workspace(N, d, which):
+    """Bytes of workspace: which = 0 for feature_stats on [N, d], 1 for feature_auroc on a group of d features.  Host arithmetic."""
+    return int(load().jamie_imputation_workspace(int(N), int(d), int(which)))
+
+
+def feature_stats(X, Y, r, mse, ws):
+    _call('jamie_feature_stats', ptr(X), ptr(Y), X.shape[0], X.shape[1], ptr(r), ptr(mse), ptr(ws), ws.numel() * ws.element_size(),
+          _stream())
+
+
+def feature_auroc(X, Y, thr, f0, dg, n_pos, U2, ws, last_stage=4):
+    _call('jamie_feature_auroc', ptr(X), ptr(Y), X.shape[0], X.shape[1], ptr(thr), int(f0), int(dg), ptr(n_pos), ptr(U2), ptr(ws),
+          ws.numel() * ws.element_size(), int(last_stage), _stream())
 
 
 class SqRanges:

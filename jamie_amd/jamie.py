@@ -74,7 +74,9 @@ class JAMIE:
                    so no N x N matrix crosses PCIe
       metrics      'host' (default): `test_closer` / `test_LabelTA` on the host with sklearn in float64, as the reference (a
                    2N x 2N distance matrix: a few thousand cells at most); 'device': on the MI355X (jamie_amd/metrics.py)
-                   in fp32 without any N x N matrix, euclidean only, for whole data sets
+                   in fp32 without any N x N matrix, euclidean only, for whole data sets.  `test_imputation` (per-feature
+                   correlation, MSE and AUROC of imputed against measured values): 'host' float64 numpy and sklearn
+                   `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts)
     """
 
     def __init__(self, match_result=None, PF_Ratio=None, corr_method='unioncom', dist_method='euclidean',
@@ -735,6 +737,48 @@ class JAMIE:
         print(f'label transfer accuracy: {acc}')
         return acc
 
+    def test_imputation(self, imputed, measured, threshold=0.0):
+        """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
+        between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
+        threshold` (a scalar or one threshold per feature) and is NaN where a feature has one class; the correlation is NaN
+        where a column is constant.  Prints the means over the features that have a figure."""
+        if self.metrics == 'device':
+            from . import imputation as jimp
+            out = jimp.imputation_metrics(imputed, measured, threshold=threshold, device=self.device)
+        else:
+            dense = [x.toarray() if hasattr(x, 'toarray') else _host_array(x) for x in (imputed, measured)]
+            out = _host_imputation_metrics(dense[0], dense[1], threshold)
+        for name in ('correlation', 'mse', 'auroc'):
+            v = out[name]
+            mean = float(np.nanmean(v)) if np.any(~np.isnan(v)) else float('nan')
+            print(f'imputation {name}: {mean}')
+        return out
+
 
 def _host_array(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _host_imputation_metrics(imputed, measured, threshold):
+    """float64 numpy for the correlation and the MSE, sklearn's `roc_auc_score` per feature."""
+    from sklearn.metrics import roc_auc_score
+    X, Y = np.asarray(imputed, dtype=np.float64), np.asarray(measured, dtype=np.float64)
+    if X.ndim != 2 or X.shape != Y.shape:
+        raise ValueError(f'test_imputation: imputed and measured values must be [cells, features] of one shape, got {X.shape} '
+                         f'and {Y.shape}')
+    N, d = X.shape
+    if N < 2 or d < 1:
+        raise ValueError(f'test_imputation: N >= 2 cells and d >= 1 features are needed, got shape {X.shape}')
+    if not (np.isfinite(X).all() and np.isfinite(Y).all()):
+        raise ValueError('test_imputation: input contains NaN or infinity')
+    thr = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (d,))
+    xc, yc = X - X.mean(0), Y - Y.mean(0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = (xc * yc).sum(0) / np.sqrt((xc * xc).sum(0) * (yc * yc).sum(0))
+    r[(np.ptp(X, axis=0) == 0) | (np.ptp(Y, axis=0) == 0)] = np.nan       # (centring a constant does not reliably leave 0)
+    auroc = np.full(d, np.nan)
+    for f in range(d):
+        label = Y[:, f] > thr[f]
+        if 0 < label.sum() < N:
+            auroc[f] = roc_auc_score(label, X[:, f])
+    return {'correlation': r, 'mse': ((X - Y) ** 2).mean(0), 'auroc': auroc}
