@@ -574,6 +574,33 @@ int jamie_feature_auroc(const float* X, const float* Y, long long N, int d, cons
                         long long* U2, void* ws, long long ws_bytes, int last_stage, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sparse cell matrices (jamie_amd/sparse_input.py): `preclass(sample, axis=0)` of the reference (utilities.py:654-678; built at
+ * jamie.py:462-465, applied at jamie.py:508 to the fitting sample and at jamie.py:806-837 to new cells in modal_predict /
+ * transform / transform_one) for a scipy CSR matrix of N cells x d features, without a dense copy of the input on the host or the
+ * device.  Stored values are fp32 (is_f64 = 0) or fp64 (is_f64 = 1); row / column pointers are int64, column indices int32, sorted
+ * within a row and without duplicates.  Deterministic: fp64 partial sums per segment of 4096 stored entries of a column, added in
+ * ascending order; no floating-point atomics; bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` (host arithmetic only, no device needed).  which = 0: jamie_csc_col_stats for the HOST array colptr[d + 1]: one
+ * fp64 partial per segment, 8 * sum over the columns of ceil(n_c / 4096).  which = 1: jamie_csr_standardise on d features: the
+ * structural-zero row, 4 d (colptr may be NULL).  0 for any other `which`, d < 1 or a decreasing colptr */
+long long jamie_sparse_workspace(const long long* colptr, int d, int which);
+/* mean[d], sd[d] (fp64, population standard deviation) from the nnz stored values in CSC order and colptr[d + 1] (device); row
+ * indices are not needed.  With n_c stored entries in column c: mean_c = (sum of the stored v) / N and
+ * sd_c = sqrt((sum of the stored (v - mean_c)^2 + (N - n_c) mean_c^2) / N), numpy's two-pass order, no term negative, divided by
+ * N.  A column without stored entries gives 0 and 0, N equal stored values give that value and 0, exactly.  seg_off[d + 1] (device,
+ * int64): seg_off[c] = number of segments of the columns before c, seg_off[d] = n_seg */
+int jamie_csc_col_stats(const void* vals, int is_f64, long long nnz, const long long* colptr, const long long* seg_off,
+                        long long n_seg, long long N, int d, double* mean, double* sd, void* ws, long long ws_bytes, void* stream);
+/* out[r, c] = (float)(((double)x - mean[c]) / sd[c]), NaN -> 0, for the CSR rows r in [0, n_rows) and c in [0, d), x = 0 where
+ * nothing is stored: jamie_standardise's expression, equal to it to the bit on the dense form of the same matrix.  out is fp32
+ * with leading dimension ld_out >= d; columns at or beyond d are not written, every other element exactly once.  A stored column
+ * index outside [0, d) is skipped, row extents are clamped to [0, nnz] */
+int jamie_csr_standardise(const long long* indptr, const int32_t* indices, const void* vals, int is_f64, long long nnz,
+                          long long n_rows, int d, const double* mean, const double* sd, float* out, long long ld_out, void* ws,
+                          long long ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

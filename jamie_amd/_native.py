@@ -7,6 +7,7 @@ pointers and launches on torch's current HIP stream.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -222,6 +223,11 @@ EXPORTS = {
                                       C.c_void_p]),
     'jamie_feature_auroc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    'jamie_sparse_workspace': (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
+    'jamie_csc_col_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_csr_standardise': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -763,6 +769,56 @@ def feature_stats(X, Y, r, mse, ws):
 def feature_auroc(X, Y, thr, f0, dg, n_pos, U2, ws, last_stage=4):
     _call('jamie_feature_auroc', ptr(X), ptr(Y), X.shape[0], X.shape[1], ptr(thr), int(f0), int(dg), ptr(n_pos), ptr(U2), ptr(ws),
           ws.numel() * ws.element_size(), int(last_stage), _stream())
+
+
+# ---- sparse cell matrices (jamie_amd/sparse_input.py; include/jamie_hip.h "Sparse cell matrices") ----
+def sparse_workspace(colptr, d, which):
+    """Bytes of workspace: which = 0 for csc_col_stats with this host `colptr` (int64 numpy [d + 1]), 1 for csr_standardise on d
+    features (colptr may be None).  Host arithmetic."""
+    if colptr is None:
+        return int(load().jamie_sparse_workspace(None, int(d), int(which)))
+    cp = np.ascontiguousarray(colptr, dtype=np.int64)
+    if cp.shape != (int(d) + 1,):
+        raise JamieHipError(f'sparse_workspace: colptr must have d + 1 = {int(d) + 1} entries, got shape {cp.shape}')
+    return int(load().jamie_sparse_workspace(cp.ctypes.data, int(d), int(which)))
+
+
+def _sparse_check(who, tensors, stats, ws):
+    if any(t.dtype != torch.float64 for t in stats):
+        raise JamieHipError(f'{who}: mean and sd must be float64')
+    if not all(t.is_contiguous() for t in tensors):
+        raise JamieHipError(f'{who}: every tensor must be contiguous')
+    if ws.dtype != torch.uint8 or (ws.numel() and ws.data_ptr() % 16):
+        raise JamieHipError(f'{who}: the workspace must be a uint8 tensor on a 16-byte boundary')
+
+
+def csc_col_stats(vals, colptr, seg_off, n_seg, N, mean, sd, ws):
+    """vals: the stored values in CSC order (fp32 / fp64), colptr / seg_off int64 [d + 1], all on the GPU; mean, sd fp64 [d]."""
+    if vals.dtype not in (torch.float32, torch.float64) or colptr.dtype != torch.int64 or seg_off.dtype != torch.int64:
+        raise JamieHipError('csc_col_stats needs fp32 / fp64 values and int64 colptr / seg_off')
+    d = mean.numel()
+    if colptr.numel() != d + 1 or seg_off.numel() != d + 1 or sd.numel() != d:
+        raise JamieHipError('csc_col_stats: colptr and seg_off have d + 1 entries, mean and sd have d')
+    _sparse_check('csc_col_stats', (vals, colptr, seg_off, mean, sd, ws), (mean, sd), ws)
+    _call('jamie_csc_col_stats', ptr(vals) if vals.numel() else None, int(vals.dtype == torch.float64), vals.numel(), ptr(colptr),
+          ptr(seg_off), int(n_seg), int(N), d, ptr(mean), ptr(sd), ptr(ws) if ws.numel() else None, ws.numel() * ws.element_size(),
+          _stream())
+
+
+def csr_standardise(indptr, indices, vals, d, mean, sd, out, ws, n_rows=None):
+    """CSR rows [0, n_rows) (int64 indptr, int32 indices, fp32 / fp64 values, on the GPU) -> out [>= n_rows, ld_out >= d] fp32."""
+    if vals.dtype not in (torch.float32, torch.float64) or indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise JamieHipError('csr_standardise needs fp32 / fp64 values, int64 indptr and int32 indices')
+    n_rows = indptr.numel() - 1 if n_rows is None else int(n_rows)
+    if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < n_rows or n_rows > indptr.numel() - 1:
+        raise JamieHipError('csr_standardise: out must be fp32 [>= n_rows, >= d] with unit column stride')
+    if indices.numel() != vals.numel() or mean.numel() != d or sd.numel() != d or out.shape[1] < d or out.stride(0) < out.shape[1]:
+        raise JamieHipError('csr_standardise: inconsistent sizes')
+    _sparse_check('csr_standardise', (indptr, indices, vals, mean, sd, ws), (mean, sd), ws)
+    nnz = vals.numel()
+    _call('jamie_csr_standardise', ptr(indptr), ptr(indices) if nnz else None, ptr(vals) if nnz else None,
+          int(vals.dtype == torch.float64), nnz, n_rows, int(d), ptr(mean), ptr(sd), ptr(out), out.stride(0), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
 
 
 class SqRanges:

@@ -31,6 +31,11 @@ _DEVICE_DISTANCE_MODES = ('geodesic', 'euclidean', 'l2', 'sqeuclidean', 'cosine'
                           'cityblock', 'chebyshev')
 
 
+def _dense_host(x):
+    """A modality as a host array: a scipy sparse matrix is densified."""
+    return x.toarray() if sp.issparse(x) else np.asarray(x)
+
+
 def init_random_seed(manual_seed):
     """unioncom.utils.init_random_seed (called at reference jamie.py:142): seeds python `random` and torch."""
     seed = random.randint(1, 10000) if manual_seed is None else manual_seed
@@ -77,6 +82,19 @@ class JAMIE:
                    in fp32 without any N x N matrix, euclidean only, for whole data sets.  `test_imputation` (per-feature
                    correlation, MSE and AUROC of imputed against measured values): 'host' float64 numpy and sklearn
                    `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts)
+      preprocess   'host' (default): `preclass` / sklearn PCA in float64 numpy on the host, the reference's arithmetic; 'device':
+                   per-feature statistics and standardisation (or randomized PCA where `pca_dim` names a dimension) on the GPU,
+                   written straight into the resident training matrices
+
+    Sparse input.  Every modality handed to `fit` / `fit_transform` / `transform` / `transform_one` / `modal_predict` (`impute`) may
+    be a scipy sparse matrix [cells, features] (any format; also behind an AnnData-like object's `.X`), of float or integer values.
+    With preprocess='device' and no `pca_dim` for that modality, fitting uploads the CSR arrays as they are: the statistics are
+    taken from the stored entries and the standardised fp32 training matrix is written on the GPU (jamie_amd/sparse_input.py), with
+    no dense copy of the INPUT on the host (the standardised fp32 cells come back as `self.dataset`, as for dense input: the
+    reference keeps the transformed cells).  With preprocess='host', or a `pca_dim` for that modality, fitting DENSIFIES ON THE HOST
+    (`X.toarray()`) and follows the dense path.  `transform` / `transform_one` / `modal_predict` stream row chunks of the CSR matrix
+    through the GPU whatever `preprocess` was, unless the modality was fitted with a PCA (then `toarray()`); the result equals the
+    dense call's.
     """
 
     def __init__(self, match_result=None, PF_Ratio=None, corr_method='unioncom', dist_method='euclidean',
@@ -259,10 +277,11 @@ class JAMIE:
 
     # ------------------------------------------------------------------------------------------
     def _build_preprocessing(self):
-        """reference jamie.py:434-469."""
+        """reference jamie.py:434-469.  A scipy sparse modality is densified on the host first."""
         pre = []
         if self.pca_dim is not None:
             for dim, data in zip(self.pca_dim, self.dataset):
+                data = _dense_host(data)
                 if dim is not None:
                     from sklearn.decomposition import PCA
                     if min(*data.shape) < dim:
@@ -277,7 +296,7 @@ class JAMIE:
                 else:
                     pre.append(preclass(np.asarray(data), axis=0))
         else:
-            pre = [preclass(np.asarray(d), axis=0) for d in self.dataset]
+            pre = [preclass(_dense_host(d), axis=0) for d in self.dataset]
         return pre
 
     def project_jamie(self, W=None):
@@ -356,6 +375,15 @@ class JAMIE:
             pre, data_dev = [], []
             dims_pca = self.pca_dim if self.pca_dim is not None else [None] * len(self.dataset)
             for dim, x in zip(dims_pca, self.dataset):
+                if sp.issparse(x):
+                    if dim is None:
+                        # CSR arrays to the GPU as they are: statistics from the stored entries, dense fp32 rows written there
+                        from .sparse_input import standardise_csr
+                        out, mean, sd = standardise_csr(x, dev)
+                        pre.append(preclass.from_stats(mean.cpu().numpy(), sd.cpu().numpy(), axis=0))
+                        data_dev.append(out)
+                        continue
+                    x = x.toarray()                                 # (no sparse PCA: densified on the host)
                 xa = np.ascontiguousarray(np.asarray(x))
                 if xa.dtype not in (np.float32, np.float64):
                     xa = xa.astype(np.float64)
@@ -375,6 +403,7 @@ class JAMIE:
                 data_dev.append(out)
             self.dataset = [d.cpu().numpy() for d in data_dev]                # the reference keeps the transformed cells
         else:
+            self.dataset = [_dense_host(x) for x in self.dataset]            # (sparse input: densified on the host, once)
             pre = self._build_preprocessing()
             self.dataset = [p.transform(np.asarray(x)) for p, x in zip(pre, self.dataset)]
         self.col = [x.shape[1] for x in self.dataset]
@@ -607,35 +636,83 @@ class JAMIE:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def modal_predict(self, data, modality, pre_transformed=False):
-        """reference jamie.py:806-815 (returns float64: the inverse scaling promotes)."""
-        assert self.model is not None, 'Model must be trained before modal prediction.'
-        to_modality = (modality + 1) % self.dataset_num
-        if not pre_transformed:
-            data = self.model.preprocessing[modality](np.asarray(data))
-        self.model.eval()
-        decoded = self.model.impute(torch.as_tensor(np.asarray(data)).float(), compose=[modality, to_modality])
-        return np.array(self.model.preprocessing_inverse[to_modality](decoded.detach().cpu()))
+    def _csr_preclass(self, i):
+        """The `preclass` of modality i if its fitted preprocessing is plain per-feature standardisation (the only kind sparse rows
+        are streamed through), else None.  It is reachable as the bound method's `__self__`, for loaded models too."""
+        pre = getattr(self.model.preprocessing[i], '__self__', None)
+        if not all(hasattr(self.model, m) for m in ('_encode_eval', '_mu_eval', '_decode_eval')):
+            return None                                            # (a model class of the caller's: `toarray()`)
+        if isinstance(pre, preclass) and pre.axis == 0 and pre.pca is None:
+            return pre
+        return None
 
-    def impute(self, data, modality, pre_transformed=False):
-        """north_star spelling of `modal_predict`."""
-        return self.modal_predict(data, modality, pre_transformed)
+    def _csr_chunks(self, data, i, pre, chunk):
+        """Standardised fp32 device rows of the sparse cells `data` of modality i, `chunk` rows at a time: the CSR arrays of a
+        chunk go up and `jamie_csr_standardise` writes (x - mean) / std, NaN -> 0, against the statistics uploaded once."""
+        from . import sparse_input as jsp
+        A = jsp.canonical_csr(data)
+        d = int(np.size(pre.mean))
+        if A.shape[1] != d:
+            raise ValueError(f'modality {i} was fitted on {d} features, the sparse input has {A.shape[1]}')
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f'chunk must be >= 1 row, got {chunk}')
+        dev = torch.device(getattr(self.model, 'device', self.device))
+        mean = torch.from_numpy(np.ascontiguousarray(np.asarray(pre.mean, dtype=np.float64).reshape(-1))).to(dev)
+        sd = torch.from_numpy(np.ascontiguousarray(np.asarray(pre.std, dtype=np.float64).reshape(-1))).to(dev)
+        for s in range(0, A.shape[0], chunk):
+            yield jsp.apply_csr(A[s:s + chunk], mean, sd, dev, canonical=True)
 
-    def transform(self, dataset, corr=None, pre_transformed=False):
-        """reference jamie.py:817-829.  In eval mode the returned embeddings are the `mu`s, so `corr` has no
-        effect ("Doesn't actually do anything", jamie.py:820) and no N x N matrix is built."""
-        if not pre_transformed:
-            dataset = [self.model.preprocessing[i](np.asarray(dataset[i])) for i in range(len(dataset))]
-        self.model.eval()
-        return [self.model.embed(torch.as_tensor(np.asarray(d)).float(), i).cpu().numpy()
-                for i, d in enumerate(dataset)]
-
-    def transform_one(self, data, i, pre_transformed=False):
-        """reference jamie.py:831-837."""
+    def _embed_input(self, data, i, pre_transformed, chunk):
+        """`mu` of modality i for dense or sparse cells: a device tensor [cells, output_dim]."""
+        if sp.issparse(data):
+            pre = None if pre_transformed else self._csr_preclass(i)
+            if pre is not None:
+                self.model.eval()
+                outs = [self.model._mu_eval(i, self.model._encode_eval(i, x)) for x in self._csr_chunks(data, i, pre, chunk)]
+                if outs:
+                    return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+            data = data.toarray()                                  # PCA preprocessing, pre-transformed or empty input
         if not pre_transformed:
             data = self.model.preprocessing[i](np.asarray(data))
         self.model.eval()
-        return self.model.embed(torch.as_tensor(np.asarray(data)).float(), i).cpu().numpy()
+        # (`chunk` goes to the model only when the caller set it: a `model_class` of the caller's may not take it)
+        kw = {} if chunk == 65536 else {'chunk': chunk}
+        return self.model.embed(torch.as_tensor(np.asarray(data)).float(), i, **kw)
+
+    def modal_predict(self, data, modality, pre_transformed=False, chunk=65536):
+        """reference jamie.py:806-815 (returns float64: the inverse scaling promotes).  `data` may be a scipy sparse matrix; `chunk`:
+        rows per pass through the network."""
+        assert self.model is not None, 'Model must be trained before modal prediction.'
+        to_modality = (modality + 1) % self.dataset_num
+        pre = self._csr_preclass(modality) if sp.issparse(data) and not pre_transformed else None
+        self.model.eval()
+        if pre is not None and data.shape[0] > 0:
+            outs = [self.model._decode_eval(to_modality, self.model._mu_eval(modality, self.model._encode_eval(modality, x)))
+                    for x in self._csr_chunks(data, modality, pre, chunk)]
+            decoded = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+        else:
+            if sp.issparse(data):
+                data = data.toarray()
+            if not pre_transformed:
+                data = self.model.preprocessing[modality](np.asarray(data))
+            kw = {} if chunk == 65536 else {'chunk': chunk}
+            decoded = self.model.impute(torch.as_tensor(np.asarray(data)).float(), compose=[modality, to_modality], **kw)
+        return np.array(self.model.preprocessing_inverse[to_modality](decoded.detach().cpu()))
+
+    def impute(self, data, modality, pre_transformed=False, chunk=65536):
+        """north_star spelling of `modal_predict`."""
+        return self.modal_predict(data, modality, pre_transformed, chunk)
+
+    def transform(self, dataset, corr=None, pre_transformed=False, chunk=65536):
+        """reference jamie.py:817-829.  In eval mode the returned embeddings are the `mu`s, so `corr` has no
+        effect ("Doesn't actually do anything", jamie.py:820) and no N x N matrix is built.  A modality may be a scipy sparse
+        matrix: its rows are streamed through the GPU `chunk` at a time (a PCA-fitted modality is densified on the host)."""
+        return [self._embed_input(d, i, pre_transformed, chunk).cpu().numpy() for i, d in enumerate(dataset)]
+
+    def transform_one(self, data, i, pre_transformed=False, chunk=65536):
+        """reference jamie.py:831-837; `data` may be a scipy sparse matrix (see `transform`)."""
+        return self._embed_input(data, i, pre_transformed, chunk).cpu().numpy()
 
     # ------------------------------------------------------------------------------------------
     def save_model(self, f):
