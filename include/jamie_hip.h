@@ -601,6 +601,35 @@ int jamie_csr_standardise(const long long* indptr, const int32_t* indices, const
                           long long ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sparse PCA products (jamie_amd/pca.py, jamie_amd/sparse_pca.py): randomized PCA of a sparse cells x features matrix X needs
+ * only products with the centred matrix Xc = X - 1 mean^T, never Xc itself:
+ *     Xc Q = X Q - 1 (mean^T Q),   Xc^T Y = X^T Y - mean (1^T Y),   Xc V^T = X V^T - 1 (mean^T V^T).
+ * jamie_csr_spmm is the sparse x dense product with that rank-one correction in its epilogue (on the CSR arrays of X for the first
+ * and third product, on the CSC arrays -- the CSR form of X^T -- for the second); jamie_weighted_colsum gives the row vector t.
+ * Arrays as in "Sparse cell matrices".  Deterministic and row-local: a row's stored entries are added in stored order in fp32; a
+ * row of more than 2048 entries is cut into segments of 2048 counted from its own start, each segment gives one fp32 partial [n]
+ * in `ws`, and the partials are added in ascending order.  No floating-point atomics: bit-identical from run to run, and a row's
+ * result is the same whether it arrives alone, in a row chunk or in the whole matrix.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` for jamie_csr_spmm (host arithmetic only) from the HOST array ptr[n_rows + 1]: positions are cut into windows of
+ * 2048 and every window has two partial slots of n floats, so 8 n ceil(nnz / 2048) with nnz = ptr[n_rows]; 0 when nnz <= 2048 (no
+ * row can be long), for n < 1, n_rows < 1 or a decreasing ptr.  A function of nnz and n alone: jamie_csr_spmm checks it */
+long long jamie_spmm_workspace(const long long* ptr, long long n_rows, int n);
+/* out[r, j] = sum over the stored entries p of row r of (float)vals[p] * B[idx[p], j], minus (s ? (float)s[r] : 1) * t[j] when t
+ * is given (one fused multiply-add), for r in [0, n_rows), j in [0, n).  B is fp32 [n_inner, ld_b >= n], out fp32 with leading
+ * dimension ld_out >= n; fp32 accumulation, fp64 values are rounded to fp32 on load.  Columns at or beyond n of `out` are not
+ * written, every other element exactly once.  A stored index outside [0, n_inner) is skipped, row extents are clamped to [0, nnz];
+ * an empty row gives -s[r] t[j] */
+int jamie_csr_spmm(const long long* ptr, const int32_t* idx, const void* vals, int is_f64, long long nnz, long long n_rows,
+                   long long n_inner, const float* B, long long ld_b, int n, const double* s /*[n_rows] or NULL = 1*/,
+                   const float* t /*[n] or NULL = no correction*/, float* out, long long ld_out, void* ws, long long ws_bytes,
+                   void* stream);
+/* t[j] = sum_r w[r] B[r, j] (w = NULL: ones) for the fp32 matrix B [rows, ld_b >= n]: fp64 partials per 512 rows added in ascending
+ * order, rounded once to fp32.  mean^T Q with w = mean, 1^T Y with w = NULL.  ws: 8 n ceil(rows / 512) bytes, 8-byte aligned */
+int jamie_weighted_colsum(const float* B, long long rows, int n, long long ld_b, const double* w /*[rows] or NULL = ones*/,
+                          float* t /*[n]*/, void* ws, long long ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

@@ -228,6 +228,12 @@ EXPORTS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_csr_standardise': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_spmm_workspace': (C.c_longlong, [C.c_void_p, C.c_longlong, C.c_int]),
+    'jamie_csr_spmm': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p,
+                                 C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                 C.c_void_p]),
+    'jamie_weighted_colsum': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_longlong, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -819,6 +825,93 @@ def csr_standardise(indptr, indices, vals, d, mean, sd, out, ws, n_rows=None):
     _call('jamie_csr_standardise', ptr(indptr), ptr(indices) if nnz else None, ptr(vals) if nnz else None,
           int(vals.dtype == torch.float64), nnz, n_rows, int(d), ptr(mean), ptr(sd), ptr(out), out.stride(0), ptr(ws),
           ws.numel() * ws.element_size(), _stream())
+
+
+# ---- sparse PCA products (jamie_amd/sparse_pca.py; include/jamie_hip.h "Sparse PCA products") ----
+COLSUM_ROWS = 512           # rows per fp64 partial of jamie_weighted_colsum (csrc/sparse_pca.hip: WCS_ROWS)
+
+
+def spmm_workspace(indptr, n):
+    """Bytes of workspace of csr_spmm with n output columns for this host `indptr` (int64 numpy [n_rows + 1]).  Host arithmetic."""
+    cp = np.ascontiguousarray(indptr, dtype=np.int64)
+    if cp.ndim != 1 or len(cp) < 1:
+        raise JamieHipError(f'spmm_workspace: indptr must be a 1-D array, got shape {cp.shape}')
+    return int(load().jamie_spmm_workspace(cp.ctypes.data, len(cp) - 1, int(n)))
+
+
+def weighted_colsum_workspace(rows, n):
+    return 8 * int(n) * (-(-int(rows) // COLSUM_ROWS))
+
+
+def _ws_bytes(who, ws, align):
+    if ws is None:
+        return 0
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or (ws.numel() and ws.data_ptr() % align):
+        raise JamieHipError(f'{who}: the workspace must be a contiguous uint8 tensor on a {align}-byte boundary')
+    return ws.numel()
+
+
+def _f32_matrix(who, what, M, n):
+    """ld of the fp32 matrix M [rows, >= n] with unit column stride."""
+    if M.dtype != torch.float32 or M.dim() != 2:
+        raise JamieHipError(f'{who}: {what} must be a 2-D float32 tensor, got {M.dtype} with {M.dim()} dimensions')
+    if M.stride(1) != 1:
+        raise JamieHipError(f'{who}: {what} must have unit column stride, got {M.stride(1)}')
+    ld = M.stride(0) if M.shape[0] > 1 else max(M.stride(0), M.shape[1])
+    if M.shape[1] < n or ld < n:
+        raise JamieHipError(f'{who}: {what} has {M.shape[1]} columns with leading dimension {ld} for n = {n}')
+    return ld
+
+
+def csr_spmm(indptr, indices, vals, n_inner, B, out, ws=None, n=None, s=None, t=None, n_rows=None):
+    """out[r, :n] = sum over the stored entries of CSR row r of value * B[index, :n], minus s[r] * t[:n] when `t` is given (s = None:
+    ones).  indptr int64, indices int32, vals fp32 / fp64, B fp32 [>= n_inner, >= n], out fp32 [>= n_rows, >= n], s fp64 [n_rows],
+    t fp32 [n]: GPU tensors, unit column stride.  `ws`: uint8, at least `spmm_workspace(indptr, n)` bytes (None where that is 0)."""
+    who = 'csr_spmm'
+    if vals.dtype not in (torch.float32, torch.float64) or indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise JamieHipError('csr_spmm needs fp32 / fp64 values, int64 indptr and int32 indices')
+    n = B.shape[1] if n is None else int(n)
+    n_rows = indptr.numel() - 1 if n_rows is None else int(n_rows)
+    nnz = vals.numel()
+    if n < 1 or n_rows < 0 or n_rows > indptr.numel() - 1 or indices.numel() != nnz:
+        raise JamieHipError(f'csr_spmm: inconsistent sizes (n = {n}, n_rows = {n_rows}, {indptr.numel()} pointers, {indices.numel()} '
+                            f'indices, {nnz} values)')
+    ld_b, ld_out = _f32_matrix(who, 'B', B, n), _f32_matrix(who, 'out', out, n)
+    if B.shape[0] < n_inner or n_inner < 1 or out.shape[0] < n_rows:
+        raise JamieHipError(f'csr_spmm: B has {B.shape[0]} rows for n_inner = {n_inner}, out {out.shape[0]} rows for n_rows = {n_rows}')
+    if s is not None and (s.dtype != torch.float64 or s.numel() < n_rows or not s.is_contiguous()):
+        raise JamieHipError('csr_spmm: s must be a contiguous float64 tensor of n_rows entries')
+    if t is not None and (t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous()):
+        raise JamieHipError('csr_spmm: t must be a contiguous float32 tensor of n entries')
+    if s is not None and t is None:
+        raise JamieHipError('csr_spmm: s without t')
+    if not all(x.is_contiguous() for x in (indptr, indices, vals)):
+        raise JamieHipError('csr_spmm: the CSR arrays must be contiguous')
+    have = _ws_bytes(who, ws, 4)
+    need = int(load().jamie_spmm_workspace((C.c_longlong * 2)(0, nnz), 1, n))          # (a function of nnz and n alone)
+    if have < need:
+        raise JamieHipError(f'csr_spmm: workspace of {have} bytes, {need} needed (spmm_workspace)')
+    _call('jamie_csr_spmm', ptr(indptr), ptr(indices) if nnz else None, ptr(vals) if nnz else None, int(vals.dtype == torch.float64),
+          nnz, n_rows, int(n_inner), ptr(B), ld_b, n, ptr(s), ptr(t), ptr(out), ld_out, ptr(ws) if have else None, have, _stream())
+
+
+def weighted_colsum(B, t, ws, w=None, n=None):
+    """t[:n] = sum_r w[r] * B[r, :n] (w = None: ones) in fp64, rounded once: B fp32 [rows, >= n], w fp64 [rows], t fp32 [n];
+    `ws`: uint8, `weighted_colsum_workspace(rows, n)` bytes."""
+    who = 'weighted_colsum'
+    n = B.shape[1] if n is None else int(n)
+    if n < 1 or B.dim() != 2 or B.shape[0] < 1:
+        raise JamieHipError(f'weighted_colsum: n >= 1 columns and >= 1 rows are needed, got n = {n}, B {tuple(B.shape)}')
+    ld_b = _f32_matrix(who, 'B', B, n)
+    rows = B.shape[0]
+    if t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous():
+        raise JamieHipError('weighted_colsum: t must be a contiguous float32 tensor of n entries')
+    if w is not None and (w.dtype != torch.float64 or w.numel() != rows or not w.is_contiguous()):
+        raise JamieHipError('weighted_colsum: w must be a contiguous float64 tensor with one entry per row of B')
+    have, need = _ws_bytes(who, ws, 8), weighted_colsum_workspace(rows, n)
+    if have < need:
+        raise JamieHipError(f'weighted_colsum: workspace of {have} bytes, {need} needed (weighted_colsum_workspace)')
+    _call('jamie_weighted_colsum', ptr(B), rows, n, ld_b, ptr(w), ptr(t), ptr(ws), have, _stream())
 
 
 class SqRanges:

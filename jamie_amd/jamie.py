@@ -88,13 +88,15 @@ class JAMIE:
 
     Sparse input.  Every modality handed to `fit` / `fit_transform` / `transform` / `transform_one` / `modal_predict` (`impute`) may
     be a scipy sparse matrix [cells, features] (any format; also behind an AnnData-like object's `.X`), of float or integer values.
-    With preprocess='device' and no `pca_dim` for that modality, fitting uploads the CSR arrays as they are: the statistics are
-    taken from the stored entries and the standardised fp32 training matrix is written on the GPU (jamie_amd/sparse_input.py), with
-    no dense copy of the INPUT on the host (the standardised fp32 cells come back as `self.dataset`, as for dense input: the
-    reference keeps the transformed cells).  With preprocess='host', or a `pca_dim` for that modality, fitting DENSIFIES ON THE HOST
-    (`X.toarray()`) and follows the dense path.  `transform` / `transform_one` / `modal_predict` stream row chunks of the CSR matrix
-    through the GPU whatever `preprocess` was, unless the modality was fitted with a PCA (then `toarray()`); the result equals the
-    dense call's.
+    With preprocess='device', fitting uploads the CSR arrays as they are, with no dense copy of the INPUT on the host or the device.
+    Without a `pca_dim` for that modality the statistics are taken from the stored entries and the standardised fp32 training matrix
+    is written on the GPU (jamie_amd/sparse_input.py); with a `pca_dim` (the default) the randomized PCA runs on the CSR / CSC arrays
+    with implicit centring (jamie_amd/pca.py, jamie_amd/sparse_pca.py) and only the [cells, pca_dim] scores are dense.  Either way
+    the fp32 training cells come back as `self.dataset`, as for dense input: the reference keeps the transformed cells.  With
+    preprocess='host' fitting DENSIFIES ON THE HOST (`X.toarray()`) and follows the dense path.  `transform` / `transform_one` /
+    `modal_predict` stream row chunks of the CSR matrix through the GPU whatever `preprocess` was -- through the PCA's components
+    for a modality fitted on the device -- unless the modality carries an sklearn PCA (preprocess='host' with a `pca_dim`: then
+    `toarray()`); the result equals the dense call's within the inference tolerance.
     """
 
     def __init__(self, match_result=None, PF_Ratio=None, corr_method='unioncom', dist_method='euclidean',
@@ -383,7 +385,18 @@ class JAMIE:
                         pre.append(preclass.from_stats(mean.cpu().numpy(), sd.cpu().numpy(), axis=0))
                         data_dev.append(out)
                         continue
-                    x = x.toarray()                                 # (no sparse PCA: densified on the host)
+                    # ... and through the PCA too: its products run on the CSR / CSC arrays (jamie_amd/sparse_pca.py)
+                    if self.model_pca != 'pca':
+                        raise NotImplementedError("model_pca='umap' needs umap-learn (absent)")
+                    if min(*x.shape) < dim:
+                        warnings.warn(f'PCA dim must be lower than {min(*x.shape)}, found {dim}, '
+                                      f'adjusting to compensate.')
+                        dim = min(*x.shape)
+                    pca = DevicePCA(dim, device=self.device)
+                    out, m, sdev = global_standardise(pca.fit_transform_device(x))
+                    pre.append(preclass.from_stats(m, sdev, axis=None, pca=pca))
+                    data_dev.append(out)
+                    continue
                 xa = np.ascontiguousarray(np.asarray(x))
                 if xa.dtype not in (np.float32, np.float64):
                     xa = xa.astype(np.float64)
@@ -663,16 +676,64 @@ class JAMIE:
         for s in range(0, A.shape[0], chunk):
             yield jsp.apply_csr(A[s:s + chunk], mean, sd, dev, canonical=True)
 
+    def _csr_pca_preclass(self, i):
+        """The `preclass` of modality i if its fitted preprocessing is a device PCA followed by the global scaling
+        (`preclass(sample, pca=pca)`, axis None, fitted with preprocess='device'), else None: an sklearn PCA takes dense input."""
+        from .pca import DevicePCA
+        pre = getattr(self.model.preprocessing[i], '__self__', None)
+        if not all(hasattr(self.model, m) for m in ('_encode_eval', '_mu_eval', '_decode_eval')):
+            return None
+        if isinstance(pre, preclass) and pre.axis is None and isinstance(pre.pca, DevicePCA):
+            return pre
+        return None
+
+    def _csr_pca_chunks(self, data, i, pre, chunk):
+        """Scaled PCA scores (fp32 device rows [rows, k]) of the sparse cells `data` of modality i, `chunk` rows at a time: the CSR
+        arrays of a chunk go up, `jamie_csr_spmm` takes them against components^T with t = mean^T components^T (uploaded once),
+        and `jamie_standardise` writes (score - m) / s, NaN -> 0."""
+        from . import sparse_input as jsp
+        from .sparse_pca import DeviceCSR, weighted_colsum
+        A = jsp.canonical_csr(data)
+        pca = pre.pca
+        k, d = pca.components_.shape
+        if A.shape[1] != d:
+            raise ValueError(f'modality {i} was fitted on {d} features, the sparse input has {A.shape[1]}')
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f'chunk must be >= 1 row, got {chunk}')
+        dev = torch.device(getattr(self.model, 'device', self.device))
+        compT = torch.from_numpy(np.ascontiguousarray(pca.components_.T.astype(np.float32))).to(dev)
+        t = weighted_colsum(compT, torch.from_numpy(np.ascontiguousarray(pca.mean_, dtype=np.float64)).to(dev))
+        m = torch.full((k,), float(pre.mean), dtype=torch.float64, device=dev)
+        s = torch.full((k,), float(pre.std), dtype=torch.float64, device=dev)
+        for lo in range(0, A.shape[0], chunk):
+            part = A[lo:lo + chunk]
+            scores = DeviceCSR(part.indptr, part.indices, part.data, d, dev).product(compT, t=t)
+            out = torch.empty_like(scores)
+            nv._call('jamie_standardise', nv.ptr(scores), 0, scores.shape[0], k, k, nv.ptr(m), nv.ptr(s), nv.ptr(out), nv._stream())
+            yield out
+
+    def _sparse_chunks(self, data, i, chunk):
+        """The standardised device rows of the sparse cells `data` as the fitted preprocessing of modality i gives them, in row
+        chunks, or None where that preprocessing takes dense input only."""
+        pre = self._csr_preclass(i)
+        if pre is not None:
+            return self._csr_chunks(data, i, pre, chunk)
+        pre = self._csr_pca_preclass(i)
+        if pre is not None:
+            return self._csr_pca_chunks(data, i, pre, chunk)
+        return None
+
     def _embed_input(self, data, i, pre_transformed, chunk):
         """`mu` of modality i for dense or sparse cells: a device tensor [cells, output_dim]."""
         if sp.issparse(data):
-            pre = None if pre_transformed else self._csr_preclass(i)
-            if pre is not None:
+            chunks = None if pre_transformed else self._sparse_chunks(data, i, chunk)
+            if chunks is not None:
                 self.model.eval()
-                outs = [self.model._mu_eval(i, self.model._encode_eval(i, x)) for x in self._csr_chunks(data, i, pre, chunk)]
+                outs = [self.model._mu_eval(i, self.model._encode_eval(i, x)) for x in chunks]
                 if outs:
                     return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
-            data = data.toarray()                                  # PCA preprocessing, pre-transformed or empty input
+            data = data.toarray()                                  # an sklearn PCA, pre-transformed or empty input
         if not pre_transformed:
             data = self.model.preprocessing[i](np.asarray(data))
         self.model.eval()
@@ -685,11 +746,11 @@ class JAMIE:
         rows per pass through the network."""
         assert self.model is not None, 'Model must be trained before modal prediction.'
         to_modality = (modality + 1) % self.dataset_num
-        pre = self._csr_preclass(modality) if sp.issparse(data) and not pre_transformed else None
+        chunks = self._sparse_chunks(data, modality, chunk) if sp.issparse(data) and not pre_transformed else None
         self.model.eval()
-        if pre is not None and data.shape[0] > 0:
+        if chunks is not None and data.shape[0] > 0:
             outs = [self.model._decode_eval(to_modality, self.model._mu_eval(modality, self.model._encode_eval(modality, x)))
-                    for x in self._csr_chunks(data, modality, pre, chunk)]
+                    for x in chunks]
             decoded = torch.cat(outs, 0) if len(outs) > 1 else outs[0]
         else:
             if sp.issparse(data):
@@ -707,7 +768,8 @@ class JAMIE:
     def transform(self, dataset, corr=None, pre_transformed=False, chunk=65536):
         """reference jamie.py:817-829.  In eval mode the returned embeddings are the `mu`s, so `corr` has no
         effect ("Doesn't actually do anything", jamie.py:820) and no N x N matrix is built.  A modality may be a scipy sparse
-        matrix: its rows are streamed through the GPU `chunk` at a time (a PCA-fitted modality is densified on the host)."""
+        matrix: its rows are streamed through the GPU `chunk` at a time (a modality fitted with an sklearn PCA, preprocess='host', is
+        densified on the host)."""
         return [self._embed_input(d, i, pre_transformed, chunk).cpu().numpy() for i, d in enumerate(dataset)]
 
     def transform_one(self, data, i, pre_transformed=False, chunk=65536):

@@ -24,10 +24,16 @@ the [N, l] side too.  What fp32 products resolve: explained variances down to ~1
 (tests/test_hip_pca.py).  Rows are processed in blocks of < 4 GiB so that the GEMM keeps its buffer-load path.
 The fitted object keeps `mean_`, `components_`, ... as float64 numpy arrays (picklable: `save_model` stores the
 preprocessing callables, jamie.py:967-968) and offers sklearn's `transform` / `inverse_transform`.
+
+A scipy sparse matrix goes through the same algorithm without a dense form of X or Xc (`SparseOperator`): the four products with
+Xc become sparse x dense products on the CSR / CSC arrays with the centring as a rank-one correction, Xc Q = X Q - 1 (mean^T Q)
+and Xc^T Y = X^T Y - mean (1^T Y) (jamie_amd/sparse_pca.py, csrc/sparse_pca.hip).  Dense input takes `DenseOperator`,
+the code above.
 """
 import math
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from . import _native as nv
@@ -150,8 +156,76 @@ def _as_device_matrix(X, device):
     return X.to(device).contiguous()
 
 
+class DenseOperator:
+    """The centred cells Xc = X - mean as an fp32 [N, d] device matrix (X: a device tensor, fp32 / fp64) and the four products
+    the fit asks of it, on the fp32 MFMA GEMM."""
+
+    def __init__(self, X):
+        self.shape = tuple(X.shape)
+        self.Xc, self.mean, self.sd = _center(X)
+
+    def right(self, Q):
+        """Xc Q: [d, l] -> [N, l]."""
+        return mm_nn(self.Xc, Q)
+
+    def left(self, Y):
+        """Xc^T Y: [N, l] -> [d, l]."""
+        return mm_tn(self.Xc, Y)
+
+    def project(self, Q):
+        """Q^T Xc: [N, l] -> [l, d]."""
+        return mm_tn(Q, self.Xc)
+
+    def scores(self, comp):
+        """Xc comp^T: [k, d] -> [N, k]."""
+        return mm_nt(self.Xc, comp)
+
+
+class SparseOperator:
+    """The same products for a scipy sparse matrix X, with the centring taken implicitly (jamie_amd/sparse_pca.py):
+    Xc Q = X Q - 1 (mean^T Q), Xc^T Y = X^T Y - mean (1^T Y).  The CSR arrays serve `right` and `scores`, the CSC arrays (with
+    their row indices: the CSR form of X^T) `left`; no [N, d] buffer exists on either side.  `mean` given (fp64 [d] on the device):
+    only `scores` is needed (transform of new cells) and the CSC arrays stay on the host."""
+
+    def __init__(self, X, device, mean=None):
+        from . import sparse_input as jsp
+        from .sparse_pca import DeviceCSR
+        A = jsp.canonical_csr(X)
+        N, d = A.shape
+        self.shape = (N, d)
+        if mean is None:
+            if N >= 2 ** 31:
+                raise ValueError(f'sparse PCA: {N} cells; the row indices of the CSC form are int32 (fewer than 2^31 cells)')
+            csc = A.tocsc()
+            self.mean, self.sd = jsp.column_stats(A, device, csc=csc)
+            self.csc = DeviceCSR(csc.indptr, csc.indices, csc.data, N, device)
+            del csc
+        else:
+            if mean.numel() != d:
+                raise ValueError(f'sparse PCA: fitted on {mean.numel()} features, the sparse input has {d}')
+            self.mean, self.sd, self.csc = mean, None, None
+        self.csr = DeviceCSR(A.indptr, A.indices, A.data, d, device)
+
+    def right(self, Q):
+        from .sparse_pca import weighted_colsum
+        Q = Q.contiguous()
+        return self.csr.product(Q, t=weighted_colsum(Q, self.mean))
+
+    def left(self, Y):
+        from .sparse_pca import weighted_colsum
+        Y = Y.contiguous()
+        return self.csc.product(Y, s=self.mean, t=weighted_colsum(Y))
+
+    def project(self, Q):
+        return self.left(Q).t().contiguous()
+
+    def scores(self, comp):
+        return self.right(comp.t().contiguous())
+
+
 class DevicePCA:
-    """`sklearn.decomposition.PCA(n_components=k)` fitted on the GPU (see the module docstring).
+    """`sklearn.decomposition.PCA(n_components=k)` fitted on the GPU (see the module docstring).  `fit*` and `transform` also take
+    a scipy sparse matrix: the products then run on its CSR / CSC arrays (`SparseOperator`) and no dense form of X is built.
 
     Attributes after `fit` (float64 numpy, sklearn's names): `mean_`, `components_` [k, d], `explained_variance_`,
     `explained_variance_ratio_`, `singular_values_`, `n_components_`, `n_samples_`, `n_features_in_`.
@@ -168,15 +242,18 @@ class DevicePCA:
     def fit_transform_device(self, X):
         nv.require_gpu()
         dev = torch.device(self.device)
-        X = _as_device_matrix(X, dev)
-        N, d = X.shape
+        if sp.issparse(X):
+            op = SparseOperator(X, dev)
+        else:
+            op = DenseOperator(_as_device_matrix(X, dev))
+        del X
+        N, d = op.shape
         k = min(self.n_components, N, d)
         ell = min(k + self.n_oversamples, N, d)
         n_iter = self.n_iter
         if n_iter == 'auto':                                   # sklearn.utils.extmath.randomized_svd
             n_iter = 7 if k < 0.1 * min(N, d) else 4
-        Xc, mean, sd = _center(X)
-        del X
+        mean, sd = op.mean, op.sd
         # sklearn's check_random_state: None = numpy's GLOBAL RandomState (so a seeded run consumes the same draws as the
         # reference's PCA(n_components) does: one normal(size=(d, k + 10)) call)
         rs = self.random_state
@@ -186,10 +263,10 @@ class DevicePCA:
             rs = np.random.RandomState(rs)
         Q = torch.from_numpy(rs.normal(size=(d, ell)).astype(np.float32)).to(dev)
         for _ in range(int(n_iter)):                           # power iterations, re-conditioned after every product
-            Q = _whiten(mm_nn(Xc, Q))                          # [N, l]
-            Q = _orth_small(mm_tn(Xc, Q))                      # [d, l]
-        Q = _whiten(mm_nn(Xc, Q), rounds=2)                    # orthonormal basis of the range of Xc, [N, l]
-        B = mm_tn(Q, Xc).double().cpu().numpy()                # [l, d]
+            Q = _whiten(op.right(Q))                           # [N, l]
+            Q = _orth_small(op.left(Q))                        # [d, l]
+        Q = _whiten(op.right(Q), rounds=2)                     # orthonormal basis of the range of Xc, [N, l]
+        B = op.project(Q).double().cpu().numpy()               # [l, d]
         _, S, Vt = np.linalg.svd(B, full_matrices=False)
         Vt, S = Vt[:k], S[:k]
         idx = np.argmax(np.abs(Vt), axis=1)                    # svd_flip(u_based_decision=False)
@@ -202,7 +279,7 @@ class DevicePCA:
         var = sd.cpu().numpy() ** 2 * (N / max(1, N - 1))     # per-feature variance, ddof = 1
         self.explained_variance_ratio_ = self.explained_variance_ / var.sum()
         comp = torch.from_numpy(np.ascontiguousarray(Vt.astype(np.float32))).to(dev)
-        return mm_nt(Xc, comp)                                 # scores = Xc V = U S, [N, k] fp32
+        return op.scores(comp)                                 # scores = Xc V = U S, [N, k] fp32
 
     def fit_transform(self, X):
         return self.fit_transform_device(X).cpu().numpy().astype(np.float64)
@@ -216,6 +293,12 @@ class DevicePCA:
         return n_rows >= 2048 and torch.cuda.is_available()
 
     def transform(self, X):
+        if sp.issparse(X):                                     # on the device whatever the row count: no dense form of X
+            nv.require_gpu()
+            dev = torch.device(self.device)
+            comp = torch.from_numpy(np.ascontiguousarray(self.components_.astype(np.float32))).to(dev)
+            op = SparseOperator(X, dev, mean=torch.from_numpy(np.ascontiguousarray(self.mean_, dtype=np.float64)).to(dev))
+            return op.scores(comp).cpu().numpy().astype(np.float64)
         X = np.asarray(X) if not torch.is_tensor(X) else X
         if not self._on_device(X.shape[0]):
             return (np.asarray(X, dtype=np.float64) - self.mean_) @ self.components_.T

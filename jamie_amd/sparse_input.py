@@ -83,13 +83,13 @@ def _stats_arg(v, d, dev, what):
     return t
 
 
-def column_stats(A, device='cuda'):
-    """(mean, sd) fp64 [d] device tensors of a canonical CSR matrix."""
+def column_stats(A, device='cuda', csc=None):
+    """(mean, sd) fp64 [d] device tensors of a canonical CSR matrix (`csc`: its `.tocsc()` where the caller already holds it)."""
     dev = torch.device(device)
     N, d = A.shape
     if N < 1 or d < 1:
         raise ValueError(f'sparse input: N >= 1 cells and d >= 1 features are needed, got shape {A.shape}')
-    csc = A.tocsc()
+    csc = A.tocsc() if csc is None else csc
     p = plan(csc.indptr)
     vals = torch.from_numpy(np.ascontiguousarray(csc.data)).to(dev)
     colptr, seg_off = _up(csc.indptr, np.int64, dev), _up(p['seg_off'], np.int64, dev)
