@@ -630,6 +630,32 @@ int jamie_weighted_colsum(const float* B, long long rows, int n, long long ld_b,
                           float* t /*[n]*/, void* ws, long long ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature impact on the device (jamie_amd/impact.py; build-defined): the mean squared change of the values imputed
+ * for modality t when ONE input feature of modality i is replaced by a background value, per feature and target column, without
+ * building the modified inputs or bringing the [features, cells, d_t] outputs to the host.  The first encoder layer is linear
+ * (model.py:151), so an occluded cell's pre-activation is H + (bg_f - x_f) W0[:, f] with H = W0 x + b taken once per cell chunk.
+ * Deterministic: no atomics, fixed summation order, bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[k n + c, m] = lrelu(bn(H[c, m] + (bg[feat[k]] - X[c, feat[k]]) * W0[m, feat[k]])) for k < g, c < n, m < h: the first hidden
+ * activation of cell c with feature feat[k] occluded, in the BatchNorm-eval + LeakyReLU expression of JAMIE_EPI_BN_EVAL
+ * ((v - mean) * (rsqrt(var + eps) * gamma) + beta, then v > 0 ? v : slope * v).  H [n, ldh >= h] fp32 is W0 x + b before
+ * BatchNorm, X [n, ldx >= d] the cells, bg [d], W0 [h, ldw >= d] (a padded first layer: ldw > d), the four BatchNorm vectors [h],
+ * out [g n, ldo >= h]; `feat` is the device copy of the host array `feat_host` [g] (unsorted, repeats allowed), which is checked
+ * against [0, d) here before anything is launched: the kernels never see an unchecked index.  ws: 4 g ceil4(h) bytes on a 16-byte
+ * boundary (the g columns of W0, transposed).  16-byte loads and stores when h, ldh and ldo are multiples of 4 and the pointers
+ * 16-byte aligned; any h otherwise.  n <= 65535 * 32, g <= 65535, g n < 2^31 */
+int jamie_occlusion_rows(const float* H, long long ldh, const float* X, long long ldx, const float* bg, const float* W0,
+                         long long ldw, const int32_t* feat /*device [g]*/, const int32_t* feat_host /*host [g]*/, int n, int h, int d,
+                         int g, const float* running_mean, const float* running_var, const float* gamma, const float* beta, float eps,
+                         float slope, float* out, long long ldo, void* ws, long long ws_bytes, void* stream);
+/* acc[k, j] += sum over c < n of ((double)Y[k n + c, j] - (double)R[c, j])^2 for k < g, j < dt: Y [g n, ldy >= dt] and
+ * R [n, ldr >= dt] fp32, acc [g, dt] fp64 (contiguous).  The cells are cut into blocks of 512; a block's 16 row groups are added
+ * in order, the blocks of an element in 32 interleaved slices, the slices in order, and one thread adds the total onto acc[k, j].
+ * ws: 8 g dt ceil(n / 512) bytes on an 8-byte boundary.  n <= 65535 * 512, g <= 65535, g n < 2^31 */
+int jamie_impact_accumulate(const float* Y, long long ldy, const float* R, long long ldr, int n, int dt, int g, double* acc, void* ws,
+                            long long ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

@@ -234,6 +234,12 @@ EXPORTS = {
                                  C.c_void_p]),
     'jamie_weighted_colsum': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_longlong, C.c_void_p]),
+    'jamie_occlusion_rows': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
+                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                       C.c_void_p]),
+    'jamie_impact_accumulate': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_longlong, C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -912,6 +918,83 @@ def weighted_colsum(B, t, ws, w=None, n=None):
     if have < need:
         raise JamieHipError(f'weighted_colsum: workspace of {have} bytes, {need} needed (weighted_colsum_workspace)')
     _call('jamie_weighted_colsum', ptr(B), rows, n, ld_b, ptr(w), ptr(t), ptr(ws), have, _stream())
+
+
+# ---- feature impact (jamie_amd/impact.py; include/jamie_hip.h "Feature impact on the device") ----
+IMPACT_ROWS = 512           # cells per fp64 partial of jamie_impact_accumulate (csrc/impact.hip: ACC_ROWS)
+
+
+def occlusion_workspace(g, h):
+    """Bytes of workspace of occlusion_rows for g features and h hidden units: the g columns of W0, transposed.  Host arithmetic."""
+    return 4 * int(g) * ((int(h) + 3) // 4 * 4)
+
+
+def impact_accumulate_workspace(n, dt, g):
+    """Bytes of workspace of impact_accumulate: one fp64 partial per block of IMPACT_ROWS cells, feature and column."""
+    return 8 * int(g) * int(dt) * (-(-int(n) // IMPACT_ROWS))
+
+
+def check_features(feat, d, who='occlusion_rows'):
+    """`feat` as a contiguous int32 numpy array [g >= 1] with every entry in [0, d), or ValueError: host arithmetic."""
+    a = np.asarray(feat)
+    if a.ndim != 1 or a.size < 1 or a.dtype.kind not in 'iu':
+        raise ValueError(f'{who}: features must be a non-empty 1-D list of integers, got shape {a.shape} and dtype {a.dtype}')
+    if int(a.min()) < 0 or int(a.max()) >= int(d):
+        raise ValueError(f'{who}: feature indices must lie in [0, {int(d)}), got {int(a.min())} .. {int(a.max())}')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def occlusion_rows(H, X, bg, W0, feat, bn, out, ws, h=None, d=None, eps=1e-5, slope=0.01, feat_dev=None):
+    """out[k n + c, :h] = lrelu(bn(H[c, :h] + (bg[feat[k]] - X[c, feat[k]]) W0[:h, feat[k]])): H [n, >= h], X [n, >= d], bg [d],
+    W0 [>= h, >= d], bn = (running mean, running var, gamma, beta) [>= h] each, out [g n, >= h]: fp32 GPU tensors with unit column
+    stride.  `feat`: host integers [g], checked against [0, d) here; `feat_dev`: their int32 device copy where the caller keeps
+    one.  `ws`: uint8, `occlusion_workspace(g, h)` bytes."""
+    who = 'occlusion_rows'
+    h = H.shape[1] if h is None else int(h)
+    d = X.shape[1] if d is None else int(d)
+    if h < 1 or d < 1 or H.dim() != 2 or H.shape[0] < 1:
+        raise JamieHipError(f'occlusion_rows: n, h, d >= 1 are needed, got H {tuple(H.shape)}, h = {h}, d = {d}')
+    n = H.shape[0]
+    f = check_features(feat, d, who)
+    g = len(f)
+    ldh, ldx, ldw, ldo = _f32_matrix(who, 'H', H, h), _f32_matrix(who, 'X', X, d), _f32_matrix(who, 'W0', W0, d), _f32_matrix(who, 'out', out, h)
+    if X.shape[0] != n or W0.shape[0] < h or out.shape[0] != g * n:
+        raise JamieHipError(f'occlusion_rows: X has {X.shape[0]} rows for n = {n}, W0 {W0.shape[0]} for h = {h}, out {out.shape[0]} for '
+                            f'g n = {g * n}')
+    for t, size, what in [(bg, d, 'bg')] + [(v, h, 'a BatchNorm vector') for v in bn]:
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < size or not t.is_contiguous():
+            raise JamieHipError(f'occlusion_rows: {what} must be a contiguous float32 vector of at least {size} entries')
+    if len(bn) != 4:
+        raise JamieHipError('occlusion_rows: bn = (running mean, running var, gamma, beta)')
+    have, need = _ws_bytes(who, ws, 16), occlusion_workspace(g, h)
+    if have < need:
+        raise JamieHipError(f'occlusion_rows: workspace of {have} bytes, {need} needed (occlusion_workspace)')
+    if feat_dev is None:
+        feat_dev = torch.from_numpy(f).to(H.device)
+    elif feat_dev.dtype != torch.int32 or feat_dev.numel() != g or not feat_dev.is_contiguous():
+        raise JamieHipError('occlusion_rows: feat_dev must be the contiguous int32 device copy of feat')
+    _call('jamie_occlusion_rows', ptr(H), ldh, ptr(X), ldx, ptr(bg), ptr(W0), ldw, ptr(feat_dev), f.ctypes.data, n, h, d, g,
+          ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), float(eps), float(slope), ptr(out), ldo, ptr(ws), have, _stream())
+
+
+def impact_accumulate(Y, R, acc, ws, dt=None):
+    """acc[k, j] += sum_c (Y[k n + c, j] - R[c, j])^2 in fp64 for j < dt: Y [g n, >= dt], R [n, >= dt] fp32 with unit column stride,
+    acc [g, dt] contiguous float64.  `ws`: uint8, `impact_accumulate_workspace(n, dt, g)` bytes."""
+    who = 'impact_accumulate'
+    dt = R.shape[1] if dt is None else int(dt)
+    if dt < 1 or R.dim() != 2 or R.shape[0] < 1:
+        raise JamieHipError(f'impact_accumulate: n, dt >= 1 are needed, got R {tuple(R.shape)}, dt = {dt}')
+    n = R.shape[0]
+    ldy, ldr = _f32_matrix(who, 'Y', Y, dt), _f32_matrix(who, 'R', R, dt)
+    if acc.dtype != torch.float64 or acc.dim() != 2 or acc.shape[1] != dt or not acc.is_contiguous() or acc.shape[0] < 1:
+        raise JamieHipError(f'impact_accumulate: acc must be a contiguous float64 tensor [g, {dt}], got {acc.dtype} {tuple(acc.shape)}')
+    g = acc.shape[0]
+    if Y.shape[0] != g * n:
+        raise JamieHipError(f'impact_accumulate: Y has {Y.shape[0]} rows for g n = {g} x {n}')
+    have, need = _ws_bytes(who, ws, 8), impact_accumulate_workspace(n, dt, g)
+    if have < need:
+        raise JamieHipError(f'impact_accumulate: workspace of {have} bytes, {need} needed (impact_accumulate_workspace)')
+    _call('jamie_impact_accumulate', ptr(Y), ldy, ptr(R), ldr, n, dt, g, ptr(acc), ptr(ws), have, _stream())
 
 
 class SqRanges:

@@ -765,6 +765,58 @@ class JAMIE:
         """north_star spelling of `modal_predict`."""
         return self.modal_predict(data, modality, pre_transformed, chunk)
 
+    def feature_impact(self, data, modality, to_modality=None, pre_transformed=False, background=None, features=None, measured=None,
+                       max_workspace=1 << 30):
+        """Occlusion impact of the input features of `modality` on the values imputed for `to_modality` (default: the next one, as in
+        `modal_predict`): the mean squared change of the imputation, in the network's standardised output space, when ONE feature
+        of every cell is set to its background value -- build-defined, see jamie_amd/impact.py.  Returns float64 numpy
+        {'impact' [F], 'per_target' [F, d_to], 'baseline' [d_to] or None}.
+
+        `pre_transformed=False`: the modality's fitted preprocessing must be per-feature standardisation (no PCA); `data` and
+        `background` are in data units (`background` defaults to the fitted mean) and `measured`, if given, goes through the
+        target modality's preprocessing.  `pre_transformed=True`: all three are in the network's own spaces and the features are
+        the network's input columns -- the only spelling for a PCA'd modality.  `data` may be a scipy sparse matrix.  `measured`
+        [cells, d_to]: the reference becomes the measured values and `baseline` is the un-occluded error.  `max_workspace`: cap in
+        bytes on the widest activation of a pass."""
+        from . import impact as jfi
+        assert self.model is not None, 'Model must be trained before feature impact.'
+        to_modality = (modality + 1) % self.dataset_num if to_modality is None else int(to_modality)
+        model = self.model
+        if not (0 <= int(modality) < self.dataset_num and 0 <= to_modality < self.dataset_num):
+            raise ValueError(f'feature_impact: modalities must lie in [0, {self.dataset_num}), got {modality} and {to_modality}')
+        if not pre_transformed:
+            pre = self._csr_preclass(modality)
+            if pre is None:
+                raise ValueError(f'feature_impact: modality {modality} was not fitted with plain per-feature standardisation (a PCA, '
+                                 'or a model class of the caller\'s), so its input features are not the data\'s; pass pre-processed '
+                                 'cells with pre_transformed=True: the features are then the network\'s input columns')
+            mean = np.asarray(pre.mean, dtype=np.float64).reshape(-1)
+            if background is not None:
+                background = np.asarray(background.cpu() if torch.is_tensor(background) else background, dtype=np.float64)
+                if background.shape != mean.shape:
+                    raise ValueError(f'feature_impact: background must be one value per feature [{mean.size}], got shape '
+                                     f'{background.shape}')
+                background = pre.transform(background)
+            if measured is not None:
+                measured = self.model.preprocessing[to_modality](np.asarray(measured.cpu() if torch.is_tensor(measured) else measured))
+            if sp.issparse(data):
+                jfi.check_arguments(model, data, modality, to_modality, background, features, measured, max_workspace)
+                chunks = list(self._csr_chunks(data, modality, pre, 65536))
+                data = torch.cat(chunks, 0) if len(chunks) > 1 else chunks[0]
+            else:
+                data = np.asarray(data.cpu() if torch.is_tensor(data) else data)
+                if data.ndim != 2 or data.shape[1] != mean.size:
+                    raise ValueError(f'feature_impact: cells must be 2-D [cells, {mean.size} features], got shape {data.shape}')
+                data = pre.transform(data)
+        elif sp.issparse(data):
+            data = data.toarray()
+        out = jfi.feature_impact(model, data, modality, to_modality, background=background, features=features, measured=measured,
+                                 max_workspace=max_workspace)
+        top = int(np.argmax(out['impact']))
+        print(f"feature impact {modality} -> {to_modality}: {len(out['impact'])} features, mean {float(out['impact'].mean())}, "
+              f"largest {float(out['impact'][top])} at position {top}")
+        return out
+
     def transform(self, dataset, corr=None, pre_transformed=False, chunk=65536):
         """reference jamie.py:817-829.  In eval mode the returned embeddings are the `mu`s, so `corr` has no
         effect ("Doesn't actually do anything", jamie.py:820) and no N x N matrix is built.  A modality may be a scipy sparse
