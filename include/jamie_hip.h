@@ -656,6 +656,42 @@ int jamie_impact_accumulate(const float* Y, long long ldy, const float* R, long 
                             long long ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Shapley attributions on the device (jamie_amd/shapley.py; build-defined): the permutation-sampling estimator of the
+ * Shapley value of F input features of modality i (the players) for the values imputed for modality t, per cell.  An order of the
+ * players is walked as removals: step m sets player f_m of every cell to its background value, and the player receives the change
+ * of the imputation.  The first encoder layer is linear (model.py:151), so a step changes a cell's pre-activation H = W0 x + b by
+ * one rank-one term: neither the masked inputs nor the d -> 2d product per prefix exist.  Deterministic: no atomics, one owner per
+ * element, fixed summation order, bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* One segment of g steps of a walk.  s_0 = state, s_m[c, :] = fmaf(-(X[c, f_m] - bg[f_m]), W0[:, f_m], s_{m-1}[c, :]) in fp32 with
+ * f_m = feat[m - 1], and out[m n + c, :h] = lrelu(bn(s_m[c, :h])) for m = 0 .. g, c < n, in the BatchNorm-eval + LeakyReLU
+ * expression of JAMIE_EPI_BN_EVAL ((v - mean) * (rsqrt(var + eps) * gamma) + beta, then v > 0 ? v : slope * v); on return `state`
+ * holds s_g, from which the next segment of the same order continues (splitting a walk into segments changes no bit of any row).
+ * state [n, lds >= h] fp32 (W0 x + b before the first segment), X [n, ldx >= d], bg [d], W0 [h, ldw >= d], the four BatchNorm
+ * vectors [h], out [(g + 1) n, ldo >= h]; `feat` is the device copy of the host array `feat_host` [g], which is checked against
+ * [0, d) here before anything is launched.  ws: 4 g ceil4(h) bytes on a 16-byte boundary (the g columns of W0, transposed, in walk
+ * order).  16-byte loads and stores when h, lds and ldo are multiples of 4 and the pointers 16-byte aligned; any h otherwise.
+ * n <= 65535 * 16, g <= 65535, (g + 1) n < 2^31 */
+int jamie_shapley_walk_rows(float* state, long long lds, const float* X, long long ldx, const float* bg, const float* W0,
+                            long long ldw, const int32_t* feat /*device [g]*/, const int32_t* feat_host /*host [g]*/, int n, int h,
+                            int d, int g, const float* running_mean, const float* running_var, const float* gamma, const float* beta,
+                            float eps, float slope, float* out, long long ldo, void* ws, long long ws_bytes, void* stream);
+/* phi[c, pos[m], j] += (double)Y[m n + c, tcol[j]] - (double)Y[(m + 1) n + c, tcol[j]] for m < g, c < n, j < T: the marginal
+ * contributions of one segment.  Y [(g + 1) n, ldy >= dt] fp32, phi [n, F, T] fp64 (contiguous).  pos [g]: positions in the player
+ * list, distinct within a launch and in [0, F); tcol [T]: distinct columns in [0, dt), or NULL for all dt columns in order
+ * (T == dt).  Both are checked here on their host copies (device copy, host copy) before anything is launched.  Every element of
+ * phi has one owner per launch: no reduction, no atomics.  (g + 1) n < 2^31, n T < 2^39 */
+int jamie_shapley_accumulate(const float* Y, long long ldy, int n, int dt, int g, const int32_t* pos /*device [g]*/,
+                             const int32_t* pos_host /*host [g]*/, int F, const int32_t* tcol /*device [T] or NULL*/,
+                             const int32_t* tcol_host /*host [T] or NULL*/, int T, double* phi, void* stream);
+/* sum_abs[e] += sum over c < n of |phi[c, e]| and sum[e] += sum over c < n of phi[c, e] for e < elems: phi [n, elems] fp64
+ * (contiguous), sum_abs and sum [elems] fp64.  The cells are cut into blocks of 512; a block's cells are added in order, then the
+ * blocks of an element in order, and one thread adds the totals onto the outputs.  ws: 16 elems ceil(n / 512) bytes on an 8-byte
+ * boundary.  n <= 65535 * 512, elems < 2^39 */
+int jamie_shapley_summarise(const double* phi, int n, long long elems, double* sum_abs, double* sum, void* ws, long long ws_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Data-parallel exchange: RCCL collectives over xGMI behind the C ABI (`jamie_allreduce`; 8(e): cells are
  * sharded by rows over one process per GPU and the flat gradient is summed over the ranks once per step, between
  * `batch_loss.backward()` (jamie.py:734) and `clip_grad_norm_` (jamie.py:739).  The reference has no distributed code.)

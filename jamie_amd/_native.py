@@ -240,6 +240,14 @@ EXPORTS = {
                                        C.c_void_p]),
     'jamie_impact_accumulate': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_shapley_walk_rows': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
+                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                          C.c_void_p]),
+    'jamie_shapley_accumulate': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_shapley_summarise': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                          C.c_void_p]),
 }
 
 # entry points of the EXPERIMENTS build only (libjamie_hip_exp.so: jamie_amd/experiments.py binds them when the loaded library has them)
@@ -995,6 +1003,111 @@ def impact_accumulate(Y, R, acc, ws, dt=None):
     if have < need:
         raise JamieHipError(f'impact_accumulate: workspace of {have} bytes, {need} needed (impact_accumulate_workspace)')
     _call('jamie_impact_accumulate', ptr(Y), ldy, ptr(R), ldr, n, dt, g, ptr(acc), ptr(ws), have, _stream())
+
+
+# ---- Shapley attributions (jamie_amd/shapley.py; include/jamie_hip.h "Shapley attributions on the device") ----
+SHAPLEY_ROWS = 512          # cells per fp64 partial of jamie_shapley_summarise (csrc/shapley.hip: SUM_ROWS)
+
+
+def shapley_walk_workspace(g, h):
+    """Bytes of workspace of shapley_walk_rows for g steps and h hidden units: the g columns of W0, transposed.  Host arithmetic."""
+    return 4 * int(g) * ((int(h) + 3) // 4 * 4)
+
+
+def shapley_summarise_workspace(n, elems):
+    """Bytes of workspace of shapley_summarise: two fp64 partials per block of SHAPLEY_ROWS cells and element."""
+    return 16 * int(elems) * (-(-int(n) // SHAPLEY_ROWS))
+
+
+def check_distinct(idx, bound, who, what):
+    """`idx` as a contiguous int32 numpy array [>= 1] of DISTINCT entries in [0, bound), or ValueError: host arithmetic."""
+    a = check_features(idx, bound, who)
+    if len(np.unique(a)) != len(a):
+        raise ValueError(f'{who}: {what} must be distinct, got {len(a) - len(np.unique(a))} repeated among {len(a)}')
+    return a
+
+
+def _device_copy(who, what, host, dev, like):
+    if dev is None:
+        return torch.from_numpy(host).to(like.device)
+    if dev.dtype != torch.int32 or dev.numel() != len(host) or not dev.is_contiguous():
+        raise JamieHipError(f'{who}: {what} must be the contiguous int32 device copy of its host array')
+    return dev
+
+
+def shapley_walk_rows(state, X, bg, W0, feat, bn, out, ws, h=None, d=None, eps=1e-5, slope=0.01, feat_dev=None):
+    """One segment of a walk: s_0 = state, s_m = fmaf(-(X[:, feat[m - 1]] - bg[feat[m - 1]]), W0[:h, feat[m - 1]], s_{m - 1}),
+    out[m n + c, :h] = lrelu(bn(s_m[c, :h])) for m = 0 .. g, and state = s_g on return.  state [n, >= h] (read and written),
+    X [n, >= d], bg [d], W0 [>= h, >= d], bn = (running mean, running var, gamma, beta) [>= h] each, out [(g + 1) n, >= h]: fp32 GPU
+    tensors with unit column stride.  `feat`: host integers [g], checked against [0, d) here; `feat_dev`: their int32 device copy
+    where the caller keeps one.  `ws`: uint8, `shapley_walk_workspace(g, h)` bytes."""
+    who = 'shapley_walk_rows'
+    h = state.shape[1] if h is None else int(h)
+    d = X.shape[1] if d is None else int(d)
+    if h < 1 or d < 1 or state.dim() != 2 or state.shape[0] < 1:
+        raise JamieHipError(f'{who}: n, h, d >= 1 are needed, got state {tuple(state.shape)}, h = {h}, d = {d}')
+    n = state.shape[0]
+    f = check_features(feat, d, who)
+    g = len(f)
+    lds, ldx, ldw, ldo = (_f32_matrix(who, 'state', state, h), _f32_matrix(who, 'X', X, d), _f32_matrix(who, 'W0', W0, d),
+                          _f32_matrix(who, 'out', out, h))
+    if X.shape[0] != n or W0.shape[0] < h or out.shape[0] != (g + 1) * n:
+        raise JamieHipError(f'{who}: X has {X.shape[0]} rows for n = {n}, W0 {W0.shape[0]} for h = {h}, out {out.shape[0]} for '
+                            f'(g + 1) n = {(g + 1) * n}')
+    if len(bn) != 4:
+        raise JamieHipError(f'{who}: bn = (running mean, running var, gamma, beta)')
+    for t, size, what in [(bg, d, 'bg')] + [(v, h, 'a BatchNorm vector') for v in bn]:
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < size or not t.is_contiguous():
+            raise JamieHipError(f'{who}: {what} must be a contiguous float32 vector of at least {size} entries')
+    have, need = _ws_bytes(who, ws, 16), shapley_walk_workspace(g, h)
+    if have < need:
+        raise JamieHipError(f'{who}: workspace of {have} bytes, {need} needed (shapley_walk_workspace)')
+    feat_dev = _device_copy(who, 'feat_dev', f, feat_dev, state)
+    _call('jamie_shapley_walk_rows', ptr(state), lds, ptr(X), ldx, ptr(bg), ptr(W0), ldw, ptr(feat_dev), f.ctypes.data, n, h, d, g,
+          ptr(bn[0]), ptr(bn[1]), ptr(bn[2]), ptr(bn[3]), float(eps), float(slope), ptr(out), ldo, ptr(ws), have, _stream())
+
+
+def shapley_accumulate(Y, pos, phi, tcol=None, dt=None, pos_dev=None, tcol_dev=None):
+    """phi[c, pos[m], j] += (double)Y[m n + c, tcol[j]] - (double)Y[(m + 1) n + c, tcol[j]]: Y [(g + 1) n, >= dt] fp32 with unit
+    column stride, phi [n, F, T] contiguous float64, `pos` host integers [g], distinct and in [0, F), `tcol` host integers [T],
+    distinct and in [0, dt), or None for all dt columns in order (T == dt).  `pos_dev`, `tcol_dev`: their int32 device copies
+    where the caller keeps them."""
+    who = 'shapley_accumulate'
+    dt = Y.shape[1] if dt is None else int(dt)
+    if phi.dtype != torch.float64 or phi.dim() != 3 or not phi.is_contiguous() or min(phi.shape) < 1:
+        raise JamieHipError(f'{who}: phi must be a contiguous float64 tensor [n, F, T], got {phi.dtype} {tuple(phi.shape)}')
+    n, F, T = phi.shape
+    if dt < 1:
+        raise JamieHipError(f'{who}: dt >= 1 is needed, got {dt}')
+    ldy = _f32_matrix(who, 'Y', Y, dt)
+    p = check_distinct(pos, F, who, 'the positions')
+    g = len(p)
+    if Y.shape[0] != (g + 1) * n:
+        raise JamieHipError(f'{who}: Y has {Y.shape[0]} rows for (g + 1) n = {g + 1} x {n}')
+    tc = None if tcol is None else check_distinct(tcol, dt, who, 'the target columns')
+    if (T != dt) if tc is None else (len(tc) != T):
+        raise JamieHipError(f'{who}: phi has {T} target columns for {dt if tc is None else len(tc)} requested')
+    pos_dev = _device_copy(who, 'pos_dev', p, pos_dev, Y)
+    tcol_dev = None if tc is None else _device_copy(who, 'tcol_dev', tc, tcol_dev, Y)
+    _call('jamie_shapley_accumulate', ptr(Y), ldy, n, dt, g, ptr(pos_dev), p.ctypes.data, F, ptr(tcol_dev),
+          None if tc is None else tc.ctypes.data, T, ptr(phi), _stream())
+
+
+def shapley_summarise(phi, sum_abs, total, ws):
+    """sum_abs[e] += sum_c |phi[c, e]| and total[e] += sum_c phi[c, e] over the leading dimension of the contiguous float64 tensor
+    `phi` [n, ...]; sum_abs and total: contiguous float64 with phi[0].numel() entries.  `ws`: uint8,
+    `shapley_summarise_workspace(n, elems)` bytes."""
+    who = 'shapley_summarise'
+    if phi.dtype != torch.float64 or phi.dim() < 2 or not phi.is_contiguous() or phi.numel() < 1:
+        raise JamieHipError(f'{who}: phi must be a non-empty contiguous float64 tensor [n, ...], got {phi.dtype} {tuple(phi.shape)}')
+    n, elems = phi.shape[0], phi[0].numel()
+    for t, what in ((sum_abs, 'sum_abs'), (total, 'total')):
+        if t.dtype != torch.float64 or t.numel() != elems or not t.is_contiguous():
+            raise JamieHipError(f'{who}: {what} must be a contiguous float64 tensor of {elems} entries, got {t.dtype} {tuple(t.shape)}')
+    have, need = _ws_bytes(who, ws, 8), shapley_summarise_workspace(n, elems)
+    if have < need:
+        raise JamieHipError(f'{who}: workspace of {have} bytes, {need} needed (shapley_summarise_workspace)')
+    _call('jamie_shapley_summarise', ptr(phi), n, elems, ptr(sum_abs), ptr(total), ptr(ws), have, _stream())
 
 
 class SqRanges:
