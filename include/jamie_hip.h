@@ -550,6 +550,30 @@ int jamie_cross_knn(const float* Q, long long Nq, const float* R, long long Nr, 
 /* pred[q] = the class code most frequent among ref_codes[idx[q, 0 .. K)] (0 <= code < n_classes), the lowest such code on a tie:
  * sklearn `KNeighborsClassifier(weights='uniform').predict` with the classes in `np.unique` order */
 int jamie_knn_vote(const int32_t* idx, long long Nq, int K, const int32_t* ref_codes, int n_classes, int32_t* pred, void* stream);
+/* Silhouette widths (jamie_amd/metrics.py `silhouette`; sklearn `silhouette_samples`) from distance sums per (cell, class).
+ * bytes of `ws` for jamie_label_distance_sums (host arithmetic only, no device needed): the work list plus the segments' partial
+ * sums, for any class sizes that add up to Nr.  seg_tiles = 0: the library's choice, which depends on Nr alone.  0 for Nq, Nr,
+ * C < 1 or seg_tiles < 0 */
+long long jamie_label_sums_workspace(long long Nq, long long Nr, int C, int seg_tiles);
+/* S[i, c] = sum over the rows j of class c of sqrt(q(i, j)), fp64 [Nq, ldS], ldS >= C (columns at or beyond C are not written).
+ * R [Nr, L] holds its rows SORTED BY CLASS: class c is rows [class_off[c], class_off[c + 1]), class_off int64 [C + 1] on the device,
+ * from 0 to Nr, not decreasing.  An empty class gives exactly 0; q(i, i) of identical rows is exactly 0, so a cell that is also a row
+ * of R adds nothing to its own class.  A workgroup walks 128-row tiles of one class (only the last one masked); sqrt(q) is added
+ * over a thread's 8 columns in fp32, then in fp64: relative error of S at most (L / 2 + 9) 2^-24.  No floating-point atomics:
+ * bit-identical from run to run, and row i's bits do not depend on where it sits in Q or on Nq.  Classes longer than seg_tiles
+ * tiles are cut into segments whose partials (in ws) are added in segment order; seg_tiles = 0: chosen by the library.  class_off
+ * is copied to the host, checked there and turned into the work list before the first launch: the call waits for `stream`.
+ * L < 1, C < 1, ldS < C, seg_tiles < 0, ws_bytes below jamie_label_sums_workspace(Nq, Nr, C, seg_tiles) or a class_off that does
+ * not end at Nr return an error before any kernel is launched */
+int jamie_label_distance_sums(const float* Q, long long Nq, const float* R, long long Nr, int L, const long long* class_off, int C,
+                              double* S, long long ldS, int seg_tiles, void* ws, long long ws_bytes, void* stream);
+/* out[i] (fp64 [Nq]) = the silhouette width of cell i among the classes [win0[i], win0[i] + wlen) (win0 int32 [Nq]; NULL: 0 for
+ * every cell; the window is clipped to [0, ldS)), own[i] (int32) its class, counts int64 [ldS] the class sizes:
+ * a = S[i, own] / (counts[own] - 1), b = min over the other non-empty classes c of the window of S[i, c] / counts[c],
+ * s = (b - a) / max(a, b); NaN where the window holds no other non-empty class (or own[i] is outside [0, ldS)), else 0 where
+ * counts[own] == 1 (sklearn's rule) or max(a, b) == 0.  One thread per cell, fp64 */
+int jamie_silhouette_widths(const double* S, long long ldS, long long Nq, const long long* counts, const int32_t* own,
+                            const int32_t* win0, int wlen, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature

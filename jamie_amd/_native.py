@@ -218,6 +218,11 @@ EXPORTS = {
     'jamie_cross_knn': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_knn_vote': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'jamie_label_sums_workspace': (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    'jamie_label_distance_sums': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_silhouette_widths': (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -773,6 +778,21 @@ def cross_knn(Q, R, K, idx, dist, ws):
 
 def knn_vote(idx, ref_codes, n_classes, pred):
     _call('jamie_knn_vote', ptr(idx), idx.shape[0], idx.shape[1], ptr(ref_codes), int(n_classes), ptr(pred), _stream())
+
+
+def label_sums_workspace(Nq, Nr, C_, seg_tiles=0):
+    """Bytes of workspace for label_distance_sums of Nq queries against Nr rows in C_ classes.  Host arithmetic."""
+    return int(load().jamie_label_sums_workspace(int(Nq), int(Nr), int(C_), int(seg_tiles)))
+
+
+def label_distance_sums(Q, R, class_off, S, ws, seg_tiles=0):
+    """S[i, c] (fp64 [Nq, >= C]) = sum of the distances of Q[i] to the rows [class_off[c], class_off[c + 1]) of R (sorted by class)."""
+    _call('jamie_label_distance_sums', ptr(Q), Q.shape[0], ptr(R), R.shape[0], Q.shape[1], ptr(class_off), class_off.numel() - 1,
+          ptr(S), S.stride(0), int(seg_tiles), ptr(ws), ws.numel() * ws.element_size(), _stream())
+
+
+def silhouette_widths(S, counts, own, win0, wlen, out):
+    _call('jamie_silhouette_widths', ptr(S), S.stride(0), S.shape[0], ptr(counts), ptr(own), ptr(win0), int(wlen), ptr(out), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

@@ -81,7 +81,10 @@ class JAMIE:
                    2N x 2N distance matrix: a few thousand cells at most); 'device': on the MI355X (jamie_amd/metrics.py)
                    in fp32 without any N x N matrix, euclidean only, for whole data sets.  `test_imputation` (per-feature
                    correlation, MSE and AUROC of imputed against measured values): 'host' float64 numpy and sklearn
-                   `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts)
+                   `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts).  `test_silhouette`
+                   (silhouette widths of the pooled cells by label, and by modality within every label; needs no paired cells):
+                   'host' sklearn `silhouette_samples` on the N x N distances in float64, 'device' jamie_amd/metrics.py
+                   `silhouette` (fp32 distances summed per cell and class in fp64, no N x N matrix)
       preprocess   'host' (default): `preclass` / sklearn PCA in float64 numpy on the host, the reference's arithmetic; 'device':
                    per-feature statistics and standardisation (or randomized PCA where `pca_dim` names a dimension) on the GPU,
                    written straight into the resident training matrices
@@ -990,6 +993,27 @@ class JAMIE:
         print(f'label transfer accuracy: {acc}')
         return acc
 
+    def test_silhouette(self, integrated_data, datatype):
+        """Silhouette widths of the pooled embeddings: by label (how well the cell types separate: `label_asw`, `label_widths`) and
+        by modality within every label (how well the modalities mix: `modality_asw`, `modality_asw_per_label`, 1 - |s| averaged,
+        NaN for a label present in fewer than two modalities), plus the label x label mean-distance matrix `label_distance` and the
+        `labels` in `np.unique` order.  Needs neither paired cells nor equal cell counts.  metrics='host': sklearn in float64 on
+        N x N distances; metrics='device': jamie_amd/metrics.py `silhouette`."""
+        if len(integrated_data) != len(datatype):
+            raise ValueError(f'test_silhouette: {len(integrated_data)} embeddings but {len(datatype)} label arrays')
+        for m, (e, lab) in enumerate(zip(integrated_data, datatype)):
+            if np.ndim(lab) != 1 or len(lab) != e.shape[0]:
+                raise ValueError(f'test_silhouette: one label per cell, got {np.shape(lab)} for the {e.shape[0]} cells of '
+                                 f'embedding {m}')
+        if self.metrics == 'device':
+            from . import metrics as jmetrics
+            out = jmetrics.silhouette(integrated_data, datatype, device=self.device)
+        else:
+            out = _host_silhouette([_host_array(e) for e in integrated_data], [np.asarray(lab) for lab in datatype])
+        print(f"label ASW: {out['label_asw']}")
+        print(f"modality ASW: {out['modality_asw']}")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1010,6 +1034,42 @@ class JAMIE:
 
 def _host_array(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _host_silhouette(embeddings, labels):
+    """The dict of `metrics.silhouette` in float64 with sklearn, on the N x N distance matrix of the pooled cells."""
+    from sklearn.metrics import silhouette_samples
+    from sklearn.metrics.pairwise import pairwise_distances
+    M = len(embeddings)
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    lab = np.concatenate(labels)
+    mod = np.repeat(np.arange(M), [len(e) for e in embeddings])
+    classes, lcode = np.unique(lab, return_inverse=True)
+    lcode = lcode.reshape(-1)
+    T = len(classes)
+    d = pairwise_distances(X, metric='euclidean')           # (raises ValueError on NaN / inf)
+    widths = silhouette_samples(d, lcode, metric='precomputed')          # (ValueError unless 2 <= T <= N - 1)
+    per_label = np.full(T, np.nan)
+    for t in range(T):
+        cells = np.nonzero(lcode == t)[0]
+        mods = mod[cells]
+        n_mod = len(np.unique(mods))
+        if n_mod < 2:
+            continue
+        if n_mod < len(cells):
+            s = silhouette_samples(d[np.ix_(cells, cells)], mods, metric='precomputed')
+        else:
+            s = np.zeros(len(cells))                        # every cell alone in its modality: sklearn's rule for singletons
+        per_label[t] = float(np.mean(1.0 - np.abs(s)))
+    have = ~np.isnan(per_label)
+    onehot = (lcode[:, None] == np.arange(T)[None, :]).astype(np.float64)
+    n = onehot.sum(axis=0)
+    G = onehot.T @ d @ onehot                               # (d is symmetric; the two products need not round alike)
+    return {'label_asw': float(np.mean(widths)), 'label_widths': widths,
+            'modality_asw': float(np.mean(per_label[have])) if have.any() else float('nan'),
+            'modality_asw_per_label': per_label,
+            'label_distance': (G + G.T) / 2 / (n[:, None] * n[None, :]),
+            'labels': classes}
 
 
 def _host_imputation_metrics(imputed, measured, threshold):
