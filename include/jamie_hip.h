@@ -576,6 +576,37 @@ int jamie_silhouette_widths(const double* S, long long ldS, long long Nq, const 
                             const int32_t* win0, int wlen, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Neighbourhoods on the device (jamie_amd/neighbors.py): the K nearest OTHER rows of one fp32 [N, L] row-major matrix, K <= 128,
+ * and the local inverse Simpson index (LISI, Korsunsky et al. 2019) on such lists.  q as in "Alignment metrics on the device": the
+ * same chain, exact on integer-valued data.  Nothing of size N x N is stored.  Deterministic: no floating-point atomics, every
+ * order fixed by position; bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` for jamie_self_knn(N, K, seg_rows): the segments' lists, S N min(K, 64) (q, index) pairs for S segments, plus one
+ * floor key per row for K > 64.  0 for N < 2, K outside 1 .. 128 or a seg_rows that jamie_self_knn refuses */
+long long jamie_self_knn_workspace(long long N, int K, long long seg_rows);
+/* For every row i of X [N, L] the K rows j != i nearest to it, ascending by (q(i, j), then lower j): idx int32 [N, K], dist fp32
+ * [N, K] = sqrtf(q).  Row i is excluded BY INDEX: a row identical to row i is a neighbour at distance 0 like any other.
+ * 1 <= K <= min(N - 1, 128), L >= 1.  K <= 64 is one pass of the workgroup of jamie_cross_knn (lists of 16 up to K = 16, of 64
+ * beyond); 64 < K is a second pass that admits only what lies above the row's 64th key (q, index) and selects the K - 64 smallest
+ * of that: (q, index) is a total order and both passes form q alike, so the two lists together are exactly the K smallest.
+ * seg_rows: rows of X per segment of the walked side, 0 (the library's choice) or a positive multiple of 128; the segments' lists
+ * are merged in segment order and the result does not depend on seg_rows.  Anything else, more than 65535 segments or a ws below
+ * jamie_self_knn_workspace(N, K, seg_rows) returns an error before a launch */
+int jamie_self_knn(const float* X, long long N, int L, int K, int32_t* idx, float* dist, long long seg_rows, void* ws,
+                   long long ws_bytes, void* stream);
+/* LISI of N cells from their neighbour lists idx int32 [N, K], dist fp32 [N, K] (jamie_self_knn; entries of idx in [0, N), one
+ * outside is read as category -1) under n_sets sets of category codes, codes int32 [n_sets, N] (any values): lisi fp64 [n_sets, N],
+ * tries int32 [N] (may be NULL) the bisection steps taken.  `compute_simpson_index` of the LISI package in fp64: with D the
+ * cell's distances as double, from beta = 1: P_j = exp(-D_j beta), s = sum P, H = log(s) + beta sum(D_j P_j) / s and P_j /= s (H = 0,
+ * P = 0 where s == 0); while |H - log(perplexity)| > 1e-5 and fewer than 50 tries, beta is doubled / halved until bracketed, then
+ * bisected.  LISI = 1 / sum over the categories of (sum of P_j over the neighbours of that category)^2, formed as sum_e P_e (sum
+ * over f with code_f == code_e of P_f); NaN in every set where the final H == 0 (every weight underflowed).  One solve per cell
+ * feeds all sets.  One wave per cell, lane l holding neighbours l and l + 64, sums by a fixed lane tree.  K < 2, K > 128, n_sets
+ * outside 1 .. 4 or a perplexity outside (1, K) return an error before a launch */
+int jamie_lisi(const int32_t* idx, const float* dist, long long N, int K, const int32_t* codes, int n_sets, double perplexity,
+               double* lisi, int32_t* tries, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
  * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
  * sums in a fixed order and integer atomics only; bit-identical from run to run.

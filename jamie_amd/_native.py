@@ -223,6 +223,11 @@ EXPORTS = {
                                             C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_silhouette_widths': (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p, C.c_void_p]),
+    'jamie_self_knn_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_longlong]),
+    'jamie_self_knn': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                 C.c_longlong, C.c_void_p]),
+    'jamie_lisi': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                             C.c_void_p, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -793,6 +798,22 @@ def label_distance_sums(Q, R, class_off, S, ws, seg_tiles=0):
 
 def silhouette_widths(S, counts, own, win0, wlen, out):
     _call('jamie_silhouette_widths', ptr(S), S.stride(0), S.shape[0], ptr(counts), ptr(own), ptr(win0), int(wlen), ptr(out), _stream())
+
+
+# ---- neighbourhoods (jamie_amd/neighbors.py; include/jamie_hip.h "Neighbourhoods on the device") ----
+def self_knn_workspace(N, K, seg_rows=0):
+    """Bytes of workspace for self_knn on N rows; 0 for arguments jamie_self_knn refuses."""
+    return int(load().jamie_self_knn_workspace(int(N), int(K), int(seg_rows)))
+
+
+def self_knn(X, K, idx, dist, ws, seg_rows=0):
+    _call('jamie_self_knn', ptr(X), X.shape[0], X.shape[1], int(K), ptr(idx), ptr(dist), int(seg_rows), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
+
+
+def lisi(idx, dist, codes, perplexity, out, tries=None):
+    _call('jamie_lisi', ptr(idx), ptr(dist), idx.shape[0], idx.shape[1], ptr(codes), codes.shape[0], float(perplexity), ptr(out),
+          ptr(tries), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

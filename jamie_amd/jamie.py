@@ -84,7 +84,11 @@ class JAMIE:
                    `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts).  `test_silhouette`
                    (silhouette widths of the pooled cells by label, and by modality within every label; needs no paired cells):
                    'host' sklearn `silhouette_samples` on the N x N distances in float64, 'device' jamie_amd/metrics.py
-                   `silhouette` (fp32 distances summed per cell and class in fp64, no N x N matrix)
+                   `silhouette` (fp32 distances summed per cell and class in fp64, no N x N matrix).  `test_lisi` (iLISI over the
+                   modality and cLISI over the label, Korsunsky et al. 2019) and `neighbors` (the kNN graph of the pooled cells
+                   as scipy CSR): 'host' float64 numpy on the N x N distances with a stable argsort, 'device'
+                   jamie_amd/neighbors.py (a self search in fp32 that excludes the cell by index, up to 128 neighbours, and
+                   the perplexity solve in fp64, no N x N matrix)
       preprocess   'host' (default): `preclass` / sklearn PCA in float64 numpy on the host, the reference's arithmetic; 'device':
                    per-feature statistics and standardisation (or randomized PCA where `pca_dim` names a dimension) on the GPU,
                    written straight into the resident training matrices
@@ -1014,6 +1018,38 @@ class JAMIE:
         print(f"modality ASW: {out['modality_asw']}")
         return out
 
+    def test_lisi(self, integrated_data, datatype=None, perplexity=30, n_neighbors=None):
+        """Local inverse Simpson index of the pooled embeddings (Korsunsky et al. 2019): `ilisi` with the modality as category
+        (how well the modalities mix around every cell: 1 to the number of modalities) and, with labels, `clisi` with the label as
+        category (how pure the cell types stay: 1 is best), their `*_median` and `*_scaled` figures in [0, 1] (1 is best for
+        both), `n_neighbors` (default min(int(3 perplexity), cells - 1), at most 128), `n_failed` (cells whose weights all
+        underflowed, NaN) and the `labels` in `np.unique` order.  Needs neither paired cells nor equal cell counts.
+        metrics='host': float64 numpy on N x N distances; metrics='device': jamie_amd/neighbors.py `lisi`."""
+        from . import neighbors as jnb
+        n_cells = [e.shape[0] for e in integrated_data]
+        perplexity, k = jnb.check_perplexity(perplexity, n_neighbors, int(sum(n_cells)), 'test_lisi')
+        jnb.pooled_codes(n_cells, datatype, 'test_lisi')
+        if self.metrics == 'device':
+            out = jnb.lisi(integrated_data, datatype, perplexity=perplexity, n_neighbors=k, device=self.device)
+        else:
+            out = _host_lisi([_host_array(e) for e in integrated_data], datatype, perplexity, k)
+        print(f"iLISI (median): {out['ilisi_median']}")
+        print(f"cLISI (median): {out['clisi_median']}")
+        return out
+
+    def neighbors(self, integrated_data, k=15, mode='distance'):
+        """The kNN graph of the pooled embeddings: scipy CSR [cells, cells] with every cell's k nearest other cells (1 <= k <=
+        min(cells - 1, 128)), nearest first, ties to the lower index; the distances as float64 (`mode='distance'`) or ones
+        (`mode='connectivity'`).  metrics='host': float64 numpy on N x N distances; metrics='device': jamie_amd/neighbors.py
+        `knn_graph`."""
+        from . import neighbors as jnb
+        if mode not in ('distance', 'connectivity'):
+            raise ValueError(f"neighbors: mode must be 'distance' or 'connectivity', not {mode!r}")
+        k = jnb.check_k(k, int(sum(e.shape[0] for e in integrated_data)), 'neighbors')
+        if self.metrics == 'device':
+            return jnb.knn_graph(integrated_data, k=k, mode=mode, device=self.device)
+        return _host_neighbors([_host_array(e) for e in integrated_data], k, mode)
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1070,6 +1106,70 @@ def _host_silhouette(embeddings, labels):
             'modality_asw_per_label': per_label,
             'label_distance': (G + G.T) / 2 / (n[:, None] * n[None, :]),
             'labels': classes}
+
+
+def _host_sorted_neighbors(embeddings, k, what):
+    """(idx int64 [N, k], dist float64 [N, k]) of the pooled cells on their N x N distance matrix: the diagonal at +inf, a stable
+    argsort.  The distances are scipy's direct differences: sklearn's `pairwise_distances` expands |x|^2 + |y|^2 - 2 x.y, which
+    loses the digits of close pairs and does not tie where the cells tie."""
+    from scipy.spatial.distance import cdist
+    if len(embeddings) < 1:
+        raise ValueError(f'{what}: no embeddings')
+    for e in embeddings:
+        if e.ndim != 2 or e.shape[1] != embeddings[0].shape[1] or e.shape[1] < 1:
+            raise ValueError(f'{what}: the embeddings must be [cells, features] with the same features')
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    if not np.isfinite(X).all():
+        raise ValueError(f'{what}: input contains NaN or infinity')
+    d = cdist(X, X)
+    np.fill_diagonal(d, np.inf)
+    order = np.argsort(d, axis=1, kind='stable')[:, :k]
+    return order, np.take_along_axis(d, order, axis=1)
+
+
+def _host_simpson(D, codes_nb, perplexity):
+    """`compute_simpson_index` of the LISI package for one cell: its k distances D, its neighbours' category codes [n_sets, k].
+    LISI per set (NaN where every weight underflowed)."""
+    def hbeta(beta):
+        P = np.exp(-D * beta)
+        s = P.sum()
+        if s == 0:
+            return 0.0, np.zeros_like(D)
+        return float(np.log(s) + beta * np.sum(D * P) / s), P / s
+    log_u = np.log(perplexity)
+    beta, bmin, bmax = 1.0, -np.inf, np.inf
+    H, P = hbeta(beta)
+    diff, tries = H - log_u, 0
+    while abs(diff) > 1e-5 and tries < 50:
+        if diff > 0:
+            bmin = beta
+            beta = beta * 2 if np.isinf(bmax) else (beta + bmax) / 2
+        else:
+            bmax = beta
+            beta = beta / 2 if np.isinf(bmin) else (beta + bmin) / 2
+        H, P = hbeta(beta)
+        diff, tries = H - log_u, tries + 1
+    if H == 0:
+        return [np.nan] * len(codes_nb)
+    return [1.0 / float(sum(P[c == b].sum() ** 2 for b in np.unique(c))) for c in codes_nb]
+
+
+def _host_lisi(embeddings, labels, perplexity, k):
+    """The dict of `neighbors.lisi` in float64 numpy, on the N x N distance matrix of the pooled cells."""
+    from . import neighbors as jnb
+    n_cells = [e.shape[0] for e in embeddings]
+    mod, lcode, classes = jnb.pooled_codes(n_cells, labels, 'test_lisi')
+    order, dist = _host_sorted_neighbors(embeddings, k, 'test_lisi')
+    codes = [mod] if lcode is None else [mod, lcode]
+    values = np.array([_host_simpson(dist[i], [c[order[i]] for c in codes], perplexity) for i in range(len(order))]).T
+    return jnb.lisi_summary(values[0], None if lcode is None else values[1], len(embeddings), classes, k)
+
+
+def _host_neighbors(embeddings, k, mode):
+    """The CSR graph of `neighbors.knn_graph` in float64 numpy, on the N x N distance matrix of the pooled cells."""
+    from . import neighbors as jnb
+    order, dist = _host_sorted_neighbors(embeddings, k, 'neighbors')
+    return jnb.graph_from_lists(order, dist, mode)
 
 
 def _host_imputation_metrics(imputed, measured, threshold):
