@@ -607,6 +607,54 @@ int jamie_lisi(const int32_t* idx, const float* dist, long long N, int K, const 
                double* lisi, int32_t* tries, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Clustering on the device (jamie_amd/clustering.py): Lloyd's k-means of one fp32 [N, L] row-major matrix with k <= 1024 centres,
+ * the two kernels of k-means++ seeding, and the contingency table of two code arrays.  q(i, j) = sum_c (X[i, c] - C[j, c])^2 as in
+ * "Alignment metrics on the device": the same chain in ascending c, exact on integer-valued data.  label[i] = argmin_j by (q, then
+ * lower j).  Nothing of size N x k is stored.  Deterministic: cluster sums are fp64 with one owner per (cluster, feature) element
+ * and a fixed order of rows, scalars are fp64 sums in a fixed order, counts are integers; no floating-point atomics; bit-identical
+ * from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` for jamie_kmeans_step(N, L, k, seg_rows) (host arithmetic only): with S = ceil(N / seg_len) segments and
+ * P = ceil(k L / 256): 8 S k L (the segments' fp64 tables) + 8 S (inertia) + 8 P (shift) + 4 S k (counts) + 4 S (changed labels),
+ * rounded up to 16.  seg_len = seg_rows, or for seg_rows = 0 whole 128-row tiles spread evenly over at most two workgroups per
+ * compute unit.  0 for arguments jamie_kmeans_step refuses */
+long long jamie_kmeans_workspace(long long N, int L, int k, long long seg_rows);
+/* One Lloyd iteration in one pass over X, unless state[0] (`done`) is raised: then every launch returns without touching anything.
+ * state int32 [4] = {done, iterations completed, converged, reserved}, zeroed by the caller before the first iteration.
+ *   assign   labels[i] (int32 [N], in place: the entry's value is the previous label) and minq[i] (fp32 [N], may be NULL) under C
+ *            (fp32 [k, L]); a workgroup owns seg_len contiguous rows and walks them in 128-row tiles against centre tiles of 128
+ *            with a running (q, j) minimum per row in registers
+ *   sum      the rows of a tile are added into an fp64 table [k, L] in ascending row order, every element by its one owner
+ *            thread; the table is in LDS while k L <= 3072, else in the segment's slab of `ws`; the segments' tables are added in
+ *            segment order: sums (fp64 [k, L], may be NULL), counts (int64 [k])
+ *   update   C[j] = (float)(sum[j] / count[j]) where `update` != 0; a cluster without a row keeps its centre
+ *   scalars  stats (fp64 [4]) = {inertia = sum of minq (the two halves of a tile by a fixed lane tree, tiles and segments in
+ *            ascending order), shift = sum ((double)C_new - (double)C_old)^2, changed labels, empty clusters}
+ *   stop     state[1] += 1 = t; done is raised where (t >= 2 and no label changed) or shift <= tol_abs (both set `converged`) or
+ *            t >= max_iter
+ * The labels, the counts and the number of iterations do not depend on seg_rows unless two centres tie within the last bit of a
+ * centre; the fp64 sums are grouped by segment, so their last bits, and through them the last bit of a centre, may.  L < 1, k
+ * outside 1 .. min(N, 1024), a seg_rows that is neither 0 nor a positive multiple of 128, max_iter < 1, tol_abs < 0 or a ws below
+ * jamie_kmeans_workspace(N, L, k, seg_rows) return an error before a launch */
+int jamie_kmeans_step(const float* X, long long N, int L, float* C, int k, int32_t* labels, float* minq, double* sums,
+                      long long* counts, double* stats, int32_t* state, double tol_abs, int max_iter, int update, long long seg_rows,
+                      void* ws, long long ws_bytes, void* stream);
+/* k-means++: with r = *row (a DEVICE int64, so that a pick never visits the host), minq[i] = q(X[i], X[r]) where `first` != 0, else
+ * min(minq[i], q(X[i], X[r])); centre (fp32 [L], may be NULL) = X[r].  r outside [0, N) leaves everything untouched */
+int jamie_kmeans_min_update(const float* X, long long N, int L, const long long* row, float* centre, float* minq, int first,
+                            void* stream);
+/* *pick (device int64) = the smallest i whose prefix sum of w (fp32 [N], >= 0) exceeds u * total, 0 <= u < 1, in this order of
+ * additions, all in fp64: the total of every block of 1024 elements by the tree v[i] += v[i + s], s = 512, 256, ..., 1 (elements
+ * past N are 0); total = the block totals added in ascending order; the block chosen is the first whose inclusive prefix of block
+ * totals (ascending) exceeds u * total, the last block if none does; inside it the elements are added in ascending order onto the
+ * block's exclusive prefix, and the first to exceed is picked (none by rounding: the block's last positive weight).  total == 0
+ * (or NaN): pick = floor(u N).  On integer-valued w below 2^53 in total every order is exact.  ws: 8 ceil(N / 1024) bytes */
+int jamie_weighted_pick(const float* w, long long N, double u, long long* pick, void* ws, long long ws_bytes, void* stream);
+/* table[a[i], b[i]] += 1 for every i (a, b int32 [N]; table int64 [na, nb], integer atomics: exact).  A pair with a code outside
+ * [0, na) x [0, nb) adds nothing and ORs 1 into *flag (device int32, zeroed by the caller) */
+int jamie_contingency(const int32_t* a, const int32_t* b, long long N, int na, int nb, long long* table, int32_t* flag, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
  * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
  * sums in a fixed order and integer atomics only; bit-identical from run to run.

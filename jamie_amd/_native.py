@@ -228,6 +228,14 @@ EXPORTS = {
                                  C.c_longlong, C.c_void_p]),
     'jamie_lisi': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                              C.c_void_p, C.c_void_p]),
+    'jamie_kmeans_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int, C.c_longlong]),
+    'jamie_kmeans_step': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
+                                    C.c_longlong, C.c_void_p]),
+    'jamie_kmeans_min_update': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p]),
+    'jamie_weighted_pick': (C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_contingency': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -814,6 +822,33 @@ def self_knn(X, K, idx, dist, ws, seg_rows=0):
 def lisi(idx, dist, codes, perplexity, out, tries=None):
     _call('jamie_lisi', ptr(idx), ptr(dist), idx.shape[0], idx.shape[1], ptr(codes), codes.shape[0], float(perplexity), ptr(out),
           ptr(tries), _stream())
+
+
+# ---- clustering (jamie_amd/clustering.py; include/jamie_hip.h "Clustering on the device") ----
+def kmeans_workspace(N, L, k, seg_rows=0):
+    """Bytes of workspace for kmeans_step; 0 for arguments jamie_kmeans_step refuses.  Host arithmetic."""
+    return int(load().jamie_kmeans_workspace(int(N), int(L), int(k), int(seg_rows)))
+
+
+def kmeans_step(X, C_, labels, counts, stats, state, ws, tol_abs=0.0, max_iter=1, update=True, minq=None, sums=None, seg_rows=0):
+    """One Lloyd iteration under the centres C_ [k, L] (see jamie_kmeans_step); a no-op once state[0] is raised."""
+    _call('jamie_kmeans_step', ptr(X), X.shape[0], X.shape[1], ptr(C_), C_.shape[0], ptr(labels), ptr(minq), ptr(sums), ptr(counts),
+          ptr(stats), ptr(state), float(tol_abs), int(max_iter), int(bool(update)), int(seg_rows), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
+
+
+def kmeans_min_update(X, row, minq, first, centre=None):
+    """minq = min(minq, q(X, X[row])) (`first`: = q) for the device int64 scalar `row`; centre [L] = X[row]."""
+    _call('jamie_kmeans_min_update', ptr(X), X.shape[0], X.shape[1], ptr(row), ptr(centre), ptr(minq), int(bool(first)), _stream())
+
+
+def weighted_pick(w, u, pick, ws):
+    """pick (device int64 scalar) = the smallest i whose prefix sum of w exceeds u * total, in the header's order of additions."""
+    _call('jamie_weighted_pick', ptr(w), w.numel(), float(u), ptr(pick), ptr(ws), ws.numel() * ws.element_size(), _stream())
+
+
+def contingency(a, b, na, nb, table, flag):
+    _call('jamie_contingency', ptr(a), ptr(b), a.numel(), int(na), int(nb), ptr(table), ptr(flag), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

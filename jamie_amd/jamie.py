@@ -1050,6 +1050,25 @@ class JAMIE:
             return jnb.knn_graph(integrated_data, k=k, mode=mode, device=self.device)
         return _host_neighbors([_host_array(e) for e in integrated_data], k, mode)
 
+    def test_clustering(self, integrated_data, datatype=None, n_clusters=None, n_init=4, max_iter=300, tol=1e-4, seed=0, init=None):
+        """k-means of the pooled embeddings and how well the clusters recover the labels: `clusters` (int32 ids,
+        one array per embedding), `centers` [k, L], `inertia`, `n_iter`, `converged`, `sizes` [k], `n_empty`, `run` (the winning
+        one of `n_init` k-means++ runs; `init` [k, L] replaces the seeding and forces one run), `modality_contingency` [k, M] and,
+        with labels, `ari`, `nmi` (sklearn's adjusted_rand_score and normalized_mutual_info_score), `contingency` [k, T] and the
+        `labels` in `np.unique` order (each None without labels).  `n_clusters` defaults to the number of distinct labels.
+        metrics='host': float64 numpy, for a few thousand cells; metrics='device': jamie_amd/clustering.py `clustering`."""
+        from . import clustering as jcl
+        k, n_init, max_iter, tol, init = jcl.check_clustering(integrated_data, datatype, n_clusters, n_init, max_iter, tol, init,
+                                                              'test_clustering')
+        if self.metrics == 'device':
+            out = jcl.clustering(integrated_data, datatype, n_clusters=k, n_init=n_init, max_iter=max_iter, tol=tol, seed=seed,
+                                 init=init, device=self.device)
+        else:
+            out = _host_clustering([_host_array(e) for e in integrated_data], datatype, k, n_init, max_iter, tol, seed, init)
+        print(f"ARI: {out['ari']}")
+        print(f"NMI: {out['nmi']}")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1170,6 +1189,69 @@ def _host_neighbors(embeddings, k, mode):
     from . import neighbors as jnb
     order, dist = _host_sorted_neighbors(embeddings, k, 'neighbors')
     return jnb.graph_from_lists(order, dist, mode)
+
+
+def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
+    """The dict of `clustering.kmeans` in float64 numpy with float64 centres: the same definition, distances by
+    direct difference (scipy's `cdist`: the expanded form loses the digits that decide between two near centres)."""
+    from scipy.spatial.distance import cdist
+    from . import clustering as jcl
+    N, L = X.shape
+    tol_abs = tol * float(np.mean(np.var(X, axis=0)))
+    best = None
+    for r in range(n_init):
+        seeds = None
+        if init is None:
+            u = jcl.seeding_stream(seed, r, k)
+            seeds = np.empty(k, np.int64)
+            seeds[0] = min(int(u[0] * N), N - 1)
+            minq = cdist(X, X[seeds[0]][None], 'sqeuclidean')[:, 0]
+            for j in range(1, k):
+                prefix = np.cumsum(minq)
+                if prefix[-1] > 0:
+                    seeds[j] = min(int(np.searchsorted(prefix, u[j] * prefix[-1], side='right')), N - 1)
+                else:
+                    seeds[j] = min(int(u[j] * N), N - 1)
+                minq = np.minimum(minq, cdist(X, X[seeds[j]][None], 'sqeuclidean')[:, 0])
+            C = X[seeds].copy()
+        else:
+            C = init.copy()
+        prev, converged = None, False
+        for t in range(1, max_iter + 1):
+            q = cdist(X, C, 'sqeuclidean')
+            lab = np.argmin(q, axis=1)                      # (the first minimum: ties to the lower centre)
+            inertia = float(q[np.arange(N), lab].sum())
+            counts = np.bincount(lab, minlength=k)
+            sums = np.zeros((k, L))
+            np.add.at(sums, lab, X)
+            new = C.copy()
+            new[counts > 0] = sums[counts > 0] / counts[counts > 0, None]
+            shift = float(((new - C) ** 2).sum())
+            same = prev is not None and np.array_equal(lab, prev)
+            C, prev = new, lab
+            if same or shift <= tol_abs:
+                converged = True
+                break
+        if best is None or inertia < best['inertia']:
+            best = {'labels': lab.astype(np.int32), 'centers': C, 'inertia': inertia, 'n_iter': t, 'converged': converged,
+                    'sizes': counts.astype(np.int64), 'n_empty': int((counts == 0).sum()), 'run': r, 'seeds': seeds}
+    return best
+
+
+def _host_clustering(embeddings, labels, k, n_init, max_iter, tol, seed, init):
+    """The dict of `clustering.clustering` in float64 numpy."""
+    from . import clustering as jcl
+    n_cells = [e.shape[0] for e in embeddings]
+    mod, lcode, classes = jcl.pooled_codes(n_cells, labels, 'test_clustering')
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    km = _host_kmeans(X, k, n_init, max_iter, tol, seed, init)
+    table_mod = np.zeros((k, len(embeddings)), np.int64)
+    np.add.at(table_mod, (km['labels'], mod), 1)
+    table_lab = None
+    if lcode is not None:
+        table_lab = np.zeros((k, len(classes)), np.int64)
+        np.add.at(table_lab, (km['labels'], lcode), 1)
+    return jcl.clustering_summary(km, n_cells, table_mod, table_lab, classes)
 
 
 def _host_imputation_metrics(imputed, measured, threshold):
