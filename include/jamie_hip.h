@@ -655,6 +655,60 @@ int jamie_weighted_pick(const float* w, long long N, double u, long long* pick, 
 int jamie_contingency(const int32_t* a, const int32_t* b, long long N, int na, int nb, long long* table, int32_t* flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Layout on the device (jamie_amd/tsne.py): t-SNE of N cells into Y fp32 [N, 2] with the EXACT gradient.  The
+ * affinities live on the neighbour lists of jamie_self_knn (idx int32 [N, K], dist fp32 [N, K], ascending, K <= 128), the joint
+ * probabilities P in a CSR matrix of O(N K) entries, and the repulsive term is a streamed pass over all pairs of Y with per-row
+ * accumulators.  Nothing of size N x N is stored.  Deterministic: no floating-point atomics, every sum has one owner and a fixed
+ * order; bit-identical from run to run at the same seg_rows.
+ * ------------------------------------------------------------------------------------------------ */
+/* Conditional affinities, sklearn's `_binary_search_perplexity` in fp64, one wave per cell (lane l holds neighbours l and l + 64,
+ * sums by a fixed xor lane tree): with e_j = d_j^2 - d_1^2 as doubles (d_1 = dist[i, 0], the nearest: s >= 1 at every beta, so no
+ * cell fails), from beta = 1: P_j = exp(-beta e_j), s = sum P, H = log(s) + beta sum(e_j P_j) / s; while |H - log(perplexity)| >
+ * 1e-5 and fewer than 100 tries, beta is doubled / halved until bracketed, then bisected.  C[i, slot] = (float)(P_j / s) fp32
+ * [N, K], beta fp64 [N], tries int32 [N].  K outside 2 .. 128 or a perplexity outside (1, K) return an error before a launch */
+int jamie_tsne_affinities(const float* dist, long long N, int K, double perplexity, float* C, double* beta, int32_t* tries,
+                          void* stream);
+/* For every (i, slot) with j = idx[i, slot]: mutual[i, slot] (int32) = 1 where i is in the list of j, and val[i, slot] (fp32) =
+ * (float)(((double)C[i -> j] + (double)C[j -> i]) / (2 N)), a missing direction counting as 0: the joint probability of the pair,
+ * the same bits from either side.  One thread per (i, slot) searching the K entries of list(j) */
+int jamie_tsne_mutual(const int32_t* idx, const float* C, long long N, int K, float* val, int32_t* mutual, void* stream);
+/* The CSR rows of P = (C + C^T) / (2 N) under rowptr int64 [N + 1]: row i holds its own K entries in neighbour order (col =
+ * idx[i, slot], value val[i, slot]), then the cells that list i without being listed by i, in ascending index.  The latter are
+ * the n_rev pairs with mutual == 0, given sorted by (target, then source): rev_pos int64 [n_rev] the flat position i K + slot of
+ * the pair, rev_tgt int32 [n_rev] its target, rev_start int64 [N + 1] the exclusive prefix of the pairs per target; rowptr[i] =
+ * i K + rev_start[i].  col int32 and pval fp32 have N K + n_rev entries; entries that would fall outside are not written */
+int jamie_tsne_fill(const int32_t* idx, const float* val, long long N, int K, const long long* rowptr, const long long* rev_pos,
+                    const int32_t* rev_tgt, const long long* rev_start, long long n_rev, int32_t* col, float* pval, void* stream);
+/* bytes of `ws` for jamie_tsne_repulsion(N, seg_rows) (host arithmetic only): with S = ceil(N / seg_len) segments, 24 S N (the
+ * segments' fp64 z, R_x, R_y per row) + 8 ceil(N / 256) (z per block of rows), each rounded up to 16.  seg_len = seg_rows, or for
+ * seg_rows = 0 whole 128-column tiles spread evenly over S = floor(1024 / ceil(N / 1024)) segments (at least 1, at most the
+ * number of tiles).  0 for arguments jamie_tsne_repulsion refuses */
+long long jamie_tsne_repulsion_workspace(long long N, long long seg_rows);
+/* With w_ij = 1 / (1 + |y_i - y_j|^2): R (fp64 [N, 2]) = sum over j != i of w_ij^2 (y_i - y_j), z (fp64 [N]) = sum over j != i of
+ * w_ij, *Z (device fp64) = sum of z.  j = i is refused BY INDEX: a point identical to point i adds w = 1 and no force.  A workgroup
+ * owns 1024 rows (four per thread, in registers) and walks one segment of the columns through LDS, 512 at a time.  fp32
+ * arithmetic (w by v_rcp_f32 and one Newton step); fp32 partial sums over runs of 32 columns, each added into fp64 accumulators;
+ * the segments' sums of a row are added in segment order; Z is the z of 256 rows by the tree v[t] += v[t + s], s = 128 .. 1, the
+ * blocks' totals by one workgroup (thread t adds blocks t, t + 256, ..., then the same tree).  The last bits may depend on
+ * seg_rows (0, or a positive multiple of 128).  Y and ws 16-byte aligned.  Anything else, more than 65535 segments or a ws below
+ * jamie_tsne_repulsion_workspace(N, seg_rows) return an error before a launch */
+int jamie_tsne_repulsion(const float* Y, long long N, double* R, double* z, double* Z, long long seg_rows, void* ws,
+                         long long ws_bytes, void* stream);
+/* bytes of `ws` for jamie_tsne_step: 16 N (a row's KL term and squared gradient) + 8 N (the gradient), each rounded up to 16 */
+long long jamie_tsne_step_workspace(long long N);
+/* The attractive term over the CSR rows of P (nnz entries), the gradient at Y, and (update != 0) sklearn's `_gradient_descent`
+ * update of Y, u, gain (fp32 [N, 2]) in place:
+ *   A_i = sum over row i of p_ij w_ij (y_i - y_j) (one wave per row: lane l takes entries l, l + 64, ... in fp32 and adds them as
+ *         doubles, the lanes by a fixed xor tree; rows of any length), grad_i = (float)(4 (alpha A_i - R_i / *Z));
+ *   per coordinate: gain = (u g < 0 ? gain + 0.2 : gain * 0.8), at least 0.01; u = momentum u - lr (gain g); y += u, in fp32.
+ * grad (fp32 [N, 2]) and A (fp64 [N, 2]) may be NULL.  kl, gsq (device fp64, both or neither): *kl = sum over the entries of
+ * p log(p (1 + d^2) *Z) and *gsq = sum of grad^2, in fp64, the rows' terms added by one workgroup in a fixed order.  Three
+ * launches (attraction + gradient, the two totals when asked, the update).  An entry whose column is outside [0, N) is skipped */
+int jamie_tsne_step(const long long* rowptr, const int32_t* col, const float* val, long long nnz, float* Y, long long N,
+                    const double* R, const double* Z, double alpha, double momentum, double lr, float* u, float* gain, int update,
+                    float* grad, double* A, double* kl, double* gsq, void* ws, long long ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
  * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
  * sums in a fixed order and integer atomics only; bit-identical from run to run.

@@ -236,6 +236,17 @@ EXPORTS = {
                                           C.c_void_p]),
     'jamie_weighted_pick': (C.c_int, [C.c_void_p, C.c_longlong, C.c_double, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_contingency': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_tsne_affinities': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_tsne_mutual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_tsne_fill': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_tsne_repulsion_workspace': (C.c_longlong, [C.c_longlong, C.c_longlong]),
+    'jamie_tsne_repulsion': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                       C.c_longlong, C.c_void_p]),
+    'jamie_tsne_step_workspace': (C.c_longlong, [C.c_longlong]),
+    'jamie_tsne_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                  C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -849,6 +860,40 @@ def weighted_pick(w, u, pick, ws):
 
 def contingency(a, b, na, nb, table, flag):
     _call('jamie_contingency', ptr(a), ptr(b), a.numel(), int(na), int(nb), ptr(table), ptr(flag), _stream())
+
+
+# ---- layout (jamie_amd/tsne.py; include/jamie_hip.h "Layout on the device") ----
+def tsne_affinities(dist, perplexity, Cout, beta, tries):
+    _call('jamie_tsne_affinities', ptr(dist), dist.shape[0], dist.shape[1], float(perplexity), ptr(Cout), ptr(beta), ptr(tries),
+          _stream())
+
+
+def tsne_mutual(idx, Cin, val, mutual):
+    _call('jamie_tsne_mutual', ptr(idx), ptr(Cin), idx.shape[0], idx.shape[1], ptr(val), ptr(mutual), _stream())
+
+
+def tsne_fill(idx, val, rowptr, rev_pos, rev_tgt, rev_start, col, pval):
+    _call('jamie_tsne_fill', ptr(idx), ptr(val), idx.shape[0], idx.shape[1], ptr(rowptr), ptr(rev_pos), ptr(rev_tgt), ptr(rev_start),
+          int(rev_pos.numel()), ptr(col), ptr(pval), _stream())
+
+
+def tsne_repulsion_workspace(N, seg_rows=0):
+    """Bytes of workspace for tsne_repulsion on N points; 0 for arguments jamie_tsne_repulsion refuses."""
+    return int(load().jamie_tsne_repulsion_workspace(int(N), int(seg_rows)))
+
+
+def tsne_repulsion(Y, R, z, Z, ws, seg_rows=0):
+    _call('jamie_tsne_repulsion', ptr(Y), Y.shape[0], ptr(R), ptr(z), ptr(Z), int(seg_rows), ptr(ws), ws.numel(), _stream())
+
+
+def tsne_step_workspace(N):
+    return int(load().jamie_tsne_step_workspace(int(N)))
+
+
+def tsne_step(rowptr, col, val, Y, R, Z, alpha, momentum, lr, u, gain, update, ws, grad=None, A=None, kl=None, gsq=None):
+    _call('jamie_tsne_step', ptr(rowptr), ptr(col), ptr(val), int(col.numel()), ptr(Y), Y.shape[0], ptr(R), ptr(Z), float(alpha),
+          float(momentum), float(lr), ptr(u), ptr(gain), int(bool(update)), ptr(grad), ptr(A), ptr(kl), ptr(gsq), ptr(ws),
+          ws.numel(), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

@@ -7,6 +7,7 @@
 // walks the rows again, admits only what lies above the query's 64th key (q, index) and selects the K - 64 smallest of that.
 // (q, index) is a total order and both passes form q by the same chain, so a candidate falls on the same side of the floor in
 // both and the concatenation is exactly the K smallest: no tie across the seam is lost or taken twice.
+#include "lane_tree.h"
 #include "pair_tile.h"
 
 namespace {
@@ -46,22 +47,7 @@ __global__ __launch_bounds__(256) void self_knn_merge_kernel(const float* __rest
 }
 
 // ---- LISI: one wave per cell, lane l holds neighbours l and l + 64; every sum over the neighbours is a fixed lane tree in fp64 ----
-__device__ __forceinline__ double wave_sum(double v) {     // (a + b and b + a are the same bits: every lane ends with the same sum)
-    v += __shfl_xor(v, 32);
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
-__device__ __forceinline__ double lane_value(double v, int src) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), src);
-    return __builtin_bit_cast(double, (long long)(((unsigned long long)hi << 32) | lo));
-}
-
+// (the fp64 lane tree `wave_sum` and `lane_value` are in lane_tree.h, shared with csrc/tsne.hip)
 // H and the normalised weights of `compute_simpson_index` (Hbeta): P_j = exp(-D_j beta), s = sum P; s == 0: H = 0, P = 0; else
 // H = log(s) + beta sum(D_j P_j) / s, P_j /= s
 __device__ __forceinline__ double entropy_at(double beta, double D0, double D1, bool have0, bool have1, double& P0, double& P1) {

@@ -1069,6 +1069,25 @@ class JAMIE:
         print(f"NMI: {out['nmi']}")
         return out
 
+    def tsne(self, integrated_data, perplexity=30, n_neighbors=None, n_iter=1000, early_exaggeration=12.0, exaggeration_iter=250,
+             learning_rate='auto', init='pca', seed=0, log_every=50, seg_rows=0):
+        """t-SNE layout of the pooled embeddings with the exact gradient: `layout` (one float32 [cells, 2] array
+        per embedding), `kl`, `kl_history` and `grad_norm_history` at the iterations `logged_at` (the multiples of `log_every`
+        below `n_iter`, and `n_iter`), `n_neighbors` (default min(int(3 perplexity), cells - 1), at most 128: a perplexity below
+        43 with the default), `learning_rate` ('auto': max(cells / early_exaggeration / 4, 50)) and `n_iter`.  sklearn's schedule
+        and gains; `init` 'pca', 'random' (from `seed`) or an array [cells, 2]; no recentring, no early stop.
+        metrics='host': float64 numpy on N x N arrays, for a few thousand cells; metrics='device': jamie_amd/tsne.py `tsne`."""
+        from . import tsne as jts
+        seg_rows = jts._check_seg_rows(seg_rows, 'tsne')
+        checked = jts.check_tsne(integrated_data, perplexity, n_neighbors, n_iter, early_exaggeration, exaggeration_iter,
+                                 learning_rate, init, log_every, 'tsne')
+        if self.metrics == 'device':
+            out = jts.tsne_checked(integrated_data, *checked, seed, self.device, seg_rows)
+        else:
+            out = _host_tsne([_host_array(e) for e in integrated_data], *checked, seed)
+        print(f"t-SNE KL divergence: {out['kl']}")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1189,6 +1208,82 @@ def _host_neighbors(embeddings, k, mode):
     from . import neighbors as jnb
     order, dist = _host_sorted_neighbors(embeddings, k, 'neighbors')
     return jnb.graph_from_lists(order, dist, mode)
+
+
+def _host_affinities(dist, perplexity):
+    """The conditional affinities of `tsne.affinities` in float64 numpy: (C [N, k], beta [N], tries [N]); sklearn's
+    `_binary_search_perplexity` on e_j = d_j^2 - d_1^2."""
+    from . import tsne as jts
+    log_u = np.log(perplexity)
+    N, k = dist.shape
+    C, betas, tries = np.empty((N, k)), np.empty(N), np.empty(N, np.int32)
+    for i in range(N):
+        e = dist[i] ** 2 - dist[i, 0] ** 2
+        beta, bmin, bmax, t = 1.0, -np.inf, np.inf, 0
+        while True:
+            P = np.exp(-beta * e)
+            s = P.sum()
+            diff = np.log(s) + beta * np.sum(e * P) / s - log_u
+            if not (abs(diff) > jts.ENTROPY_TOL and t < jts.MAX_TRIES):
+                break
+            if diff > 0:
+                bmin = beta
+                beta = beta * 2 if np.isinf(bmax) else (beta + bmax) / 2
+            else:
+                bmax = beta
+                beta = beta / 2 if np.isinf(bmin) else (beta + bmin) / 2
+            t += 1
+        C[i], betas[i], tries[i] = P / s, beta, t
+    return C, betas, tries
+
+
+def _host_joint(order, C):
+    """P = (C + C^T) / (2N) as a dense float64 [N, N] matrix."""
+    N = len(order)
+    cond = np.zeros((N, N))
+    np.put_along_axis(cond, order, C, axis=1)
+    return (cond + cond.T) / (2.0 * N)
+
+
+def _host_gradient(P, Y, alpha):
+    """(grad [N, 2], Z, KL) of DESIGN.md §19 in float64 on N x N arrays."""
+    from scipy.spatial.distance import cdist
+    W = 1.0 / (1.0 + cdist(Y, Y, 'sqeuclidean'))
+    np.fill_diagonal(W, 0.0)
+    Z = float(W.sum())
+    PW, W2 = P * W, W * W
+    A = PW.sum(axis=1)[:, None] * Y - PW @ Y
+    R = W2.sum(axis=1)[:, None] * Y - W2 @ Y
+    nz = P > 0
+    kl = float(np.sum(P[nz] * np.log(P[nz] * Z / W[nz])))
+    return 4.0 * (alpha * A - R / Z), Z, kl
+
+
+def _host_tsne(embeddings, perplexity, k, n_iter, early_exaggeration, exaggeration_iter, learning_rate, init, log_every, seed):
+    """The dict of `tsne.tsne` in float64 numpy on N x N arrays: the same definition from the same initial layout
+    (the PCA init is taken of the cells rounded to fp32, which is what the device route holds)."""
+    from . import tsne as jts
+    n_cells = [e.shape[0] for e in embeddings]
+    order, dist = _host_sorted_neighbors(embeddings, k, 'tsne')
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    C, _, _ = _host_affinities(dist, perplexity)
+    P = _host_joint(order, C)
+    Y = jts.initial_layout(X.astype(np.float32), init, seed).astype(np.float64)
+    u, gain = np.zeros_like(Y), np.ones_like(Y)
+    phases, logged_at = jts.schedule(n_iter, exaggeration_iter, early_exaggeration, log_every)
+    kl_hist, gsq_hist = [], []
+    for t, (alpha, momentum) in enumerate(phases):
+        g, _, kl = _host_gradient(P, Y, alpha)
+        if t in logged_at:
+            kl_hist.append(kl)
+            gsq_hist.append(float(np.sum(g * g)))
+        gain = np.maximum(np.where(u * g < 0, gain + 0.2, gain * 0.8), 0.01)
+        u = momentum * u - learning_rate * (gain * g)
+        Y = Y + u
+    g, _, kl = _host_gradient(P, Y, 1.0)
+    kl_hist.append(kl)
+    gsq_hist.append(float(np.sum(g * g)))
+    return jts.tsne_summary(Y, n_cells, kl_hist, gsq_hist, logged_at, k, learning_rate, n_iter)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
