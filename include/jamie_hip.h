@@ -709,6 +709,45 @@ int jamie_tsne_step(const long long* rowptr, const int32_t* col, const float* va
                     float* grad, double* A, double* kl, double* gsq, void* ws, long long ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * UMAP layout on the device (jamie_amd/umap.py): the fuzzy neighbour graph of N cells on the lists of
+ * jamie_self_knn (idx int32 [N, K], dist fp32 [N, K], nearest first, K = n_neighbors - 1 <= 128) and the stochastic layout epochs
+ * over its CSR rows (the layout of jamie_tsne_fill).  O(N K) memory.  Deterministic: no floating-point atomics; every sum and
+ * every entry of the schedule has one owner; bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* Smooth kNN distances, umap-learn's `smooth_knn_dist` in fp64, one wave per cell (lane l holds neighbours l and l + 64, sums by
+ * the fixed xor lane tree): rho = the smallest positive distance of the row (0 if none); psi_j(s) = exp(-(d_j - rho) / s) where
+ * d_j - rho > 0, else 1; from lo = 0, hi = inf, mid = 1 and for at most 64 tries: sum = sum_j psi_j(mid); stop if |sum - target| <
+ * 1e-5; if sum > target, hi = mid and mid = (lo + hi) / 2; else lo = mid and mid is doubled while hi is infinite, else (lo + hi) /
+ * 2.  sigma = max(mid, 1e-3 (sum of the row's K distances) / n_neighbors).  W[i, slot] (fp32 [N, K]) = 1 where d - rho <= 0 or
+ * sigma == 0, else (float)exp(-(d - rho) / sigma); rho, sigma fp64 [N]; tries int32 [N] = the sums evaluated (1 .. 64).  `target`
+ * is log2(n_neighbors), passed by the caller so that both routes of jamie_amd/umap.py use one double */
+int jamie_umap_smooth_knn(const float* dist, long long N, int K, int n_neighbors, double target, float* W, double* rho,
+                          double* sigma, int32_t* tries, void* stream);
+/* jamie_tsne_mutual with the fuzzy union: for every (i, slot) with j = idx[i, slot], mutual[i, slot] = 1 where i is in the list of
+ * j, and val[i, slot] = (float)((a + b) - a b) with a = (double)W[i -> j], b = (double)W[j -> i] (0 if j does not list i): the same
+ * bits from either side.  jamie_tsne_fill then writes the CSR rows */
+int jamie_umap_mutual(const int32_t* idx, const float* W, long long N, int K, float* val, int32_t* mutual, void* stream);
+/* One synchronous epoch `epoch` (0-based) over the CSR graph (rowptr int64 [N + 1], col int32 [nnz]; symmetric to the bit) in one
+ * launch: every read of the layout is from Y_in, every write goes to Y_out (fp32 [N, 2] each, two buffers).
+ *   schedule  entry e fires iff next[e] <= (float)epoch; then next[e] += eps[e] (fp32 [nnz] each; eps = +inf never fires).
+ *   draws     draw r < negative_sample_rate of entry e: word r & 3 of Philox4x32-10 with counter (e & 0xffffffff, e >> 32, epoch,
+ *             r >> 2) and key (seed & 0xffffffff, seed >> 32); the cell k = (word N) >> 32; k == i adds nothing.
+ *   move      with d2 = fma(dx, dx, dy dy), p = powf(d2, b), q = fma(a, p, 1), clip to [-4, 4] per coordinate and coefficients
+ *             0 where d2 == 0:  attraction c = ((float)(-2 a b) p) / (d2 q);  repulsion c = (float)(2 gamma b) / ((0.001 + d2) q);
+ *             entry sum s = 2 clip(c_att (y_i - y_j)) + clip(c_rep (y_i - y_k0)) + clip(c_rep (y_i - y_k1)) + ... in that order;
+ *             delta_i = the sum of s over the firing entries of row i;  Y_out[i] = fma((float)alpha, delta_i, Y_in[i]).
+ * The factor 2 stands for the `move_other` half of entry (j, i), which fires in the same epochs.  Sixteen lanes own a row of any
+ * length: lane l takes entries l, l + 16, ... in ascending order into one fp32 partial sum per coordinate, the sixteen partial
+ * sums are added by the xor tree 8, 4, 2, 1, and one lane writes.  No scratch, no LDS.  delta (fp32 [N, 2]), fired (int32 [N],
+ * the row's firing entries of this epoch) and fired_total (int64 [N], to which the same count is ADDED) may be NULL.  An entry
+ * whose column is outside [0, N) fires but moves nothing: the entry point cannot read device memory, so `umap.epoch` and
+ * `umap.optimize` check the columns of a graph once.  Y_in == Y_out, N outside [2, 2^31), a, b, gamma <= 0, alpha < 0 or a
+ * negative_sample_rate outside 1 .. 64 return an error before a launch */
+int jamie_umap_epoch(const long long* rowptr, const int32_t* col, const float* eps, float* next, long long nnz, const float* Y_in,
+                     float* Y_out, long long N, int epoch, double alpha, double a, double b, double gamma, int negative_sample_rate,
+                     unsigned long long seed, float* delta, int32_t* fired, long long* fired_total, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
  * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
  * sums in a fixed order and integer atomics only; bit-identical from run to run.

@@ -247,6 +247,12 @@ EXPORTS = {
     'jamie_tsne_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                   C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_umap_smooth_knn': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    'jamie_umap_mutual': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_umap_epoch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
+                                   C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -894,6 +900,23 @@ def tsne_step(rowptr, col, val, Y, R, Z, alpha, momentum, lr, u, gain, update, w
     _call('jamie_tsne_step', ptr(rowptr), ptr(col), ptr(val), int(col.numel()), ptr(Y), Y.shape[0], ptr(R), ptr(Z), float(alpha),
           float(momentum), float(lr), ptr(u), ptr(gain), int(bool(update)), ptr(grad), ptr(A), ptr(kl), ptr(gsq), ptr(ws),
           ws.numel(), _stream())
+
+
+# ---- UMAP layout (jamie_amd/umap.py; include/jamie_hip.h "UMAP layout on the device") ----
+def umap_smooth_knn(dist, n_neighbors, target, W, rho, sigma, tries):
+    _call('jamie_umap_smooth_knn', ptr(dist), dist.shape[0], dist.shape[1], int(n_neighbors), float(target), ptr(W), ptr(rho),
+          ptr(sigma), ptr(tries), _stream())
+
+
+def umap_mutual(idx, W, val, mutual):
+    _call('jamie_umap_mutual', ptr(idx), ptr(W), idx.shape[0], idx.shape[1], ptr(val), ptr(mutual), _stream())
+
+
+def umap_epoch(rowptr, col, eps, nxt, Y_in, Y_out, epoch, alpha, a, b, gamma, negative_sample_rate, seed, delta=None, fired=None,
+               fired_total=None):
+    _call('jamie_umap_epoch', ptr(rowptr), ptr(col), ptr(eps), ptr(nxt), int(col.numel()), ptr(Y_in), ptr(Y_out), Y_in.shape[0],
+          int(epoch), float(alpha), float(a), float(b), float(gamma), int(negative_sample_rate), int(seed) & 0xffffffffffffffff,
+          ptr(delta), ptr(fired), ptr(fired_total), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

@@ -14,6 +14,7 @@
 //
 // Deterministic: no floating-point atomics; every sum has one owner and a fixed order.
 #include "lane_tree.h"
+#include "mutual.h"
 
 namespace {
 
@@ -80,16 +81,8 @@ __global__ __launch_bounds__(256) void tsne_mutual_kernel(const int32_t* __restr
     if (e >= N * K) return;
     const long long i = e / K;
     const long long j = idx[e];
-    double other = 0.0;
-    int m = 0;
-    if (j >= 0 && j < N) {
-        for (int s = 0; s < K; ++s)
-            if (idx[j * K + s] == i) {
-                other = (double)C[j * K + s];
-                m = 1;
-                break;
-            }
-    }
+    double other;
+    const int m = mutual_search(idx, C, N, K, i, j, other);
     val[e] = (float)(((double)C[e] + other) / (2.0 * (double)N));
     mutual[e] = m;
 }

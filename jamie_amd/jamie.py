@@ -1088,6 +1088,24 @@ class JAMIE:
         print(f"t-SNE KL divergence: {out['kl']}")
         return out
 
+    def umap(self, integrated_data, n_neighbors=15, min_dist=0.1, spread=1.0, n_epochs=None, learning_rate=1.0,
+             negative_sample_rate=5, repulsion_strength=1.0, init='pca', seed=0, a=None, b=None, return_graph=False):
+        """UMAP layout of the pooled embeddings: `layout` (one float32 [cells, 2] array per embedding), the curve
+        `a`, `b` (fitted to `min_dist` and `spread` unless given), `n_epochs` (default 500 up to 10 000 cells, else 200),
+        `n_neighbors`, `n_edges` (stored entries of the fuzzy graph), `n_fired` (entries fired over all epochs) and `graph` (the
+        fuzzy graph, scipy CSR float32, with `return_graph`; else None).  Synchronous epochs, exactly `negative_sample_rate` draws
+        per firing, `init` 'pca', 'random' (from `seed`) or an array [cells, 2].
+        metrics='host': float64 numpy on N x N arrays, for a few thousand cells; metrics='device': jamie_amd/umap.py `umap`."""
+        from . import umap as jum
+        checked = jum.check_umap(integrated_data, n_neighbors, min_dist, spread, n_epochs, learning_rate, negative_sample_rate,
+                                 repulsion_strength, init, a, b, 'umap')
+        if self.metrics == 'device':
+            out = jum.umap_checked(integrated_data, *checked, seed, return_graph, self.device)
+        else:
+            out = _host_umap([_host_array(e) for e in integrated_data], *checked, seed, return_graph)
+        print(f"UMAP: {out['n_edges']} edges, {out['n_fired']} firings over {out['n_epochs']} epochs")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1284,6 +1302,113 @@ def _host_tsne(embeddings, perplexity, k, n_iter, early_exaggeration, exaggerati
     kl_hist.append(kl)
     gsq_hist.append(float(np.sum(g * g)))
     return jts.tsne_summary(Y, n_cells, kl_hist, gsq_hist, logged_at, k, learning_rate, n_iter)
+
+
+def _host_smooth_knn(dist, n_neighbors):
+    """`umap.smooth_knn` in float64 numpy: (W float32 [N, k], rho [N], sigma [N], tries [N]); umap-learn's `smooth_knn_dist`
+    bisection with the sigma floor of DESIGN.md §20."""
+    from . import umap as jum
+    dist = np.asarray(dist, dtype=np.float64)
+    N, k = dist.shape
+    target = jum.smooth_target(n_neighbors)
+    W, rho, sigma, tries = np.empty((N, k), np.float32), np.empty(N), np.empty(N), np.empty(N, np.int32)
+    for i in range(N):
+        d = dist[i]
+        pos = d[d > 0]
+        r = float(pos.min()) if pos.size else 0.0
+        e = d - r
+        lo, hi, mid, t = 0.0, np.inf, 1.0, 0
+        while t < jum.MAX_TRIES:
+            s = float(np.sum(np.where(e > 0, np.exp(-np.maximum(e, 0.0) / mid), 1.0)))
+            t += 1
+            if abs(s - target) < jum.SUM_TOL:
+                break
+            if s > target:
+                hi = mid
+                mid = (lo + hi) / 2
+            else:
+                lo = mid
+                mid = mid * 2 if np.isinf(hi) else (lo + hi) / 2
+        sg = max(mid, jum.SIGMA_FLOOR * float(d.sum()) / n_neighbors)
+        W[i] = np.where((e <= 0) | (sg == 0), 1.0, np.exp(-np.maximum(e, 0.0) / (sg if sg > 0 else 1.0)))
+        rho[i], sigma[i], tries[i] = r, sg, t
+    return W, rho, sigma, tries
+
+
+def _host_fuzzy_graph(order, W):
+    """A = W + W^T - W o W^T of the lists `order` [N, k] and their fp32 weights W as CSR arrays (rowptr int64, col int32, val
+    float32) in the row order of DESIGN.md §20: a row's own k entries in neighbour order, then the cells that list it without
+    being listed by it, ascending."""
+    N, k = order.shape
+    dense = np.zeros((N, N))
+    listed = np.zeros((N, N), dtype=bool)
+    np.put_along_axis(dense, order, np.asarray(W, dtype=np.float64), axis=1)
+    np.put_along_axis(listed, order, True, axis=1)
+    A = ((dense + dense.T) - dense * dense.T).astype(np.float32)
+    rev = listed.T & ~listed
+    cols = [np.concatenate([order[i], np.nonzero(rev[i])[0]]) for i in range(N)]
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum([len(c) for c in cols])
+    col = np.concatenate(cols).astype(np.int32)
+    row = np.repeat(np.arange(N), np.diff(rowptr))
+    return rowptr, col, A[row, col]
+
+
+def _host_umap_epoch(row, col, eps, nxt, Y, n, alpha, a, b, gamma, negative_sample_rate, seed):
+    """Epoch n of DESIGN.md §20 in float64 on the layout Y [N, 2]: (the layout after it, the entries fired).  `nxt` (float32)
+    advances in place; `row` is the row of every CSR entry."""
+    from . import umap as jum
+    N = len(Y)
+    fire = nxt <= np.float32(n)
+    nxt[fire] = nxt[fire] + eps[fire]
+    e = np.nonzero(fire)[0]
+    i, j = row[e], col[e]
+
+    def powers(d):
+        d2 = np.sum(d * d, axis=1)
+        safe = np.where(d2 > 0, d2, 1.0)
+        return d2, safe, safe ** b
+
+    d = Y[i] - Y[j]
+    d2, safe, p = powers(d)
+    c = np.where(d2 > 0, -2.0 * a * b * (p / safe) / (1.0 + a * p), 0.0)
+    move = 2.0 * np.clip(c[:, None] * d, -4.0, 4.0)
+    cells = jum.negative_cells(seed, e, n, negative_sample_rate, N)
+    for r in range(negative_sample_rate):
+        k = cells[:, r]
+        d = Y[i] - Y[k]
+        d2, safe, p = powers(d)
+        c = np.where((d2 > 0) & (k != i), 2.0 * gamma * b / ((0.001 + safe) * (1.0 + a * p)), 0.0)
+        move += np.clip(c[:, None] * d, -4.0, 4.0)
+    delta = np.stack([np.bincount(i, weights=move[:, 0], minlength=N), np.bincount(i, weights=move[:, 1], minlength=N)], axis=1)
+    return Y + alpha * delta, len(e)
+
+
+def _host_umap(embeddings, n_neighbors, n_epochs, learning_rate, negative_sample_rate, repulsion_strength, init, a, b, seed,
+               return_graph=False):
+    """The dict of `umap.umap` in float64 numpy on N x N arrays: the same definition with the same draws, the
+    same fp32 schedule, the same a, b and the same initial layout (the PCA init is taken of the cells rounded to fp32, which is
+    what the device route holds)."""
+    from . import umap as jum
+    n_cells = [e.shape[0] for e in embeddings]
+    order, dist = _host_sorted_neighbors(embeddings, n_neighbors - 1, 'umap')
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    W, _, _, _ = _host_smooth_knn(dist, n_neighbors)
+    rowptr, col, val = _host_fuzzy_graph(order, W)
+    row = np.repeat(np.arange(len(X)), np.diff(rowptr))
+    eps, nxt = jum.schedule_arrays(val, n_epochs)
+    Y = jum.initial_layout(X.astype(np.float32), init, seed).astype(np.float64)
+    a32, b32 = jum.curve32(a, b)
+    n_fired = 0
+    for n in range(n_epochs):
+        Y, fired = _host_umap_epoch(row, col, eps, nxt, Y, n, jum.alpha_of(learning_rate, n, n_epochs), a32, b32, repulsion_strength,
+                                    negative_sample_rate, seed)
+        n_fired += fired
+    graph = None
+    if return_graph:
+        from scipy.sparse import csr_matrix
+        graph = csr_matrix((val, col, rowptr), shape=(len(X), len(X)))
+    return jum.umap_summary(Y, n_cells, a, b, n_epochs, n_neighbors, len(col), n_fired, graph)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
