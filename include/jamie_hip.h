@@ -748,6 +748,43 @@ int jamie_umap_epoch(const long long* rowptr, const int32_t* col, const float* e
                      unsigned long long seed, float* delta, int32_t* fired, long long* fired_total, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Spectral embedding on the device (jamie_amd/spectral.py): the products of a Chebyshev-filtered subspace
+ * iteration for the leading eigenvectors of S = diag(s) A diag(s), A the CSR fuzzy graph above (rowptr int64 [N + 1], col int32,
+ * val fp32 [nnz]; symmetric to the bit), s one fp64 scale per cell.  Blocks are fp64 [N, B] row-major, B = 16 or 32: a row is one
+ * or two 128-byte lines.  Together they stand where umap-learn calls `umap.spectral.spectral_layout` (scipy.sparse.linalg.eigsh
+ * of the normalised Laplacian) and scanpy calls `Neighbors.compute_eigen`.  O(nnz + N B) memory.  Deterministic: no atomics;
+ * every sum has one owner and a fixed order; bit-identical from run to run.  1 <= N < 2^31 throughout.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[i] = sum_j A_ij w[j] in fp64 (w == NULL: w = 1), the degree d = A 1 of `spectral_layout` / `compute_transitions`.  Sixteen
+ * lanes own a row: lane l adds (double)val[e] * w[col[e]] for its entries l, l + 16, ... in ascending order (a product, then a
+ * sum: no fma), the sixteen partial sums by the xor tree 8, 4, 2, 1.  An entry whose column is outside [0, N) is skipped */
+int jamie_graph_rowsum(const long long* rowptr, const int32_t* col, const float* val, const double* w, long long N, long long nnz,
+                       double* out, void* stream);
+/* The operator apply of eigsh's matvec, one step of the three-term recurrence in one launch:
+ *   out[i, l] = ((alpha scale[i]) acc + gamma in[i, l]) - beta prev[i, l],   acc = sum over the entries e of row i, ascending, of
+ *   ((double)val[e] scale[col[e]]) in[col[e], l]      (every product and sum rounded on its own: no fma)
+ * B lanes own a row (4 rows per wave at B = 16, 2 at B = 32) and lane l owns column l; the group loads B entries at a time, one per
+ * lane, and hands (col, val scale) round by __shfl in entry order; no atomics, no LDS allocation, no scratch.  prev may
+ * be NULL (the last term is then left out) and out may be prev: every element is read by its one owner before it is written.
+ * out == in, prev == in, a B other than 16 or 32 or a NaN coefficient return an error before a launch.  An entry whose column
+ * is outside [0, N) contributes nothing and reads nothing; `spectral.cheb_step` checks the columns of a graph once */
+int jamie_graph_cheb_step(const long long* rowptr, const int32_t* col, const float* val, long long nnz, const double* scale,
+                          const double* in, const double* prev, double* out, long long N, int B, double alpha, double gamma,
+                          double beta, void* stream);
+/* bytes of `ws` for jamie_block_gram: ceil(N / 512) B B doubles (host arithmetic; 0 for arguments it refuses) */
+long long jamie_block_gram_workspace(long long N, int B);
+/* out = Y^T Z, fp64 [B, B] (the Rayleigh quotient X^T S X and the Gram matrix of the orthonormalisation; LOBPCG's and ARPACK's
+ * dense inner products).  Segments of 512 rows whatever the device: within a segment element (a, b) is the chain acc = fma(Y[r,
+ * a], Z[r, b], acc) over the rows ascending, by one thread; the segments' sums are added in segment order by one workgroup.
+ * Y == Z is allowed and gives a matrix symmetric to the bit.  `out` and `ws` differ from the blocks */
+int jamie_block_gram(const double* Y, const double* Z, long long N, int B, void* ws, long long ws_bytes, double* out, void* stream);
+/* out = Y1 M1 (+ Y2 M2 when both are given), M fp64 [B, B] row-major on the device: the Ritz rotation X V, the orthonormalising
+ * Y (U w^-1/2) and the residual S X - X Theta.  One owner per element: a1 = fma(Y1[i, c], M1[c, l], a1) for c = 0 .. B - 1, a2
+ * likewise, out = a1 + a2.  `out` differs from every input */
+int jamie_block_rotate(const double* Y1, const double* M1, const double* Y2, const double* M2, long long N, int B, double* out,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Imputation metrics on the device (jamie_amd/imputation.py; SURVEY.md row 12, the reference's evaluation.py): per-feature
  * figures between an imputed matrix X and the measured matrix Y, both fp32 [N, d] row-major and finite.  Deterministic: fp64
  * sums in a fixed order and integer atomics only; bit-identical from run to run.

@@ -253,6 +253,13 @@ EXPORTS = {
     'jamie_umap_epoch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong,
                                    C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_ulonglong, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_graph_rowsum': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p,
+                                     C.c_void_p]),
+    'jamie_graph_cheb_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    'jamie_block_gram_workspace': (C.c_longlong, [C.c_longlong, C.c_int]),
+    'jamie_block_gram': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'jamie_block_rotate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     'jamie_imputation_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     'jamie_feature_stats': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                       C.c_void_p]),
@@ -917,6 +924,29 @@ def umap_epoch(rowptr, col, eps, nxt, Y_in, Y_out, epoch, alpha, a, b, gamma, ne
     _call('jamie_umap_epoch', ptr(rowptr), ptr(col), ptr(eps), ptr(nxt), int(col.numel()), ptr(Y_in), ptr(Y_out), Y_in.shape[0],
           int(epoch), float(alpha), float(a), float(b), float(gamma), int(negative_sample_rate), int(seed) & 0xffffffffffffffff,
           ptr(delta), ptr(fired), ptr(fired_total), _stream())
+
+
+# ---- spectral embedding (jamie_amd/spectral.py; include/jamie_hip.h "Spectral embedding on the device") ----
+def graph_rowsum(rowptr, col, val, w, out):
+    _call('jamie_graph_rowsum', ptr(rowptr), ptr(col), ptr(val), ptr(w), out.shape[0], int(col.numel()), ptr(out), _stream())
+
+
+def graph_cheb_step(rowptr, col, val, scale, X, prev, out, alpha, gamma, beta):
+    _call('jamie_graph_cheb_step', ptr(rowptr), ptr(col), ptr(val), int(col.numel()), ptr(scale), ptr(X), ptr(prev), ptr(out),
+          X.shape[0], X.shape[1], float(alpha), float(gamma), float(beta), _stream())
+
+
+def block_gram_workspace(N, B):
+    """Bytes of workspace for block_gram on [N, B] blocks; 0 for arguments jamie_block_gram refuses.  Host arithmetic."""
+    return int(load().jamie_block_gram_workspace(int(N), int(B)))
+
+
+def block_gram(Y, Z, ws, out):
+    _call('jamie_block_gram', ptr(Y), ptr(Z), Y.shape[0], Y.shape[1], ptr(ws), ws.numel() * ws.element_size(), ptr(out), _stream())
+
+
+def block_rotate(Y1, M1, Y2, M2, out):
+    _call('jamie_block_rotate', ptr(Y1), ptr(M1), ptr(Y2), ptr(M2), Y1.shape[0], Y1.shape[1], ptr(out), _stream())
 
 
 # ---- imputation metrics (jamie_amd/imputation.py; include/jamie_hip.h "Imputation metrics on the device") ----

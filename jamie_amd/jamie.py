@@ -1106,6 +1106,27 @@ class JAMIE:
         print(f"UMAP: {out['n_edges']} edges, {out['n_fired']} firings over {out['n_epochs']} epochs")
         return out
 
+    def spectral(self, integrated_data, n_components=2, n_neighbors=15, kind='laplacian', density_normalize=None, tol=1e-8,
+                 max_iter=100, max_degree=60, seed=0, return_graph=False):
+        """Spectral embedding of the pooled embeddings: the eigenvectors of the `n_components` + 1 largest
+        eigenvalues of the normalised fuzzy graph of `umap` -- umap-learn's spectral layout (`kind='laplacian'`) or scanpy's
+        diffusion map (`kind='diffmap'`, which turns `density_normalize` on unless it is given).  `vectors` (one float64 [cells,
+        n_components + 1] array per embedding, the trivial vector first), `embedding` (the same without it), `eigenvalues`,
+        `residuals`, `degree`, `umap_init` (float32 [cells, 2] for `umap(init=...)`), `converged`, `iterations`, `applies`,
+        `degrees`, `n_neighbors`, `n_edges` and `graph` (scipy CSR with `return_graph`).  `spectral.pseudotime(out, root)` gives
+        the diffusion pseudotime.  metrics='host': float64 numpy on N x N arrays and `numpy.linalg.eigh`, for a few thousand
+        cells; metrics='device': jamie_amd/spectral.py `spectral`."""
+        from . import spectral as jsp
+        checked = jsp.check_spectral(integrated_data, n_components, n_neighbors, kind, density_normalize, tol, max_iter, max_degree,
+                                     'spectral')
+        if self.metrics == 'device':
+            out = jsp.spectral_checked(integrated_data, *checked, seed, return_graph, self.device)
+        else:
+            out = _host_spectral([_host_array(e) for e in integrated_data], *checked, return_graph)
+        print(f"spectral: eigenvalues {out['eigenvalues'][0]:.6f} .. {out['eigenvalues'][-1]:.6f}, largest residual "
+              f"{out['residuals'].max():.2e}, {out['applies']} applies")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1409,6 +1430,39 @@ def _host_umap(embeddings, n_neighbors, n_epochs, learning_rate, negative_sample
         from scipy.sparse import csr_matrix
         graph = csr_matrix((val, col, rowptr), shape=(len(X), len(X)))
     return jum.umap_summary(Y, n_cells, a, b, n_epochs, n_neighbors, len(col), n_fired, graph)
+
+
+def _host_spectral(embeddings, n_components, n_neighbors, kind, density_normalize, tol, max_iter, max_degree, return_graph=False):
+    """The dict of `spectral.spectral` in float64 numpy on N x N arrays: the same graph, degree and scale, then
+    `numpy.linalg.eigh` of the dense S.  No iteration: `iterations` and `applies` are 0."""
+    from . import spectral as jsp
+    n_cells = [e.shape[0] for e in embeddings]
+    order, dist = _host_sorted_neighbors(embeddings, n_neighbors - 1, 'spectral')
+    N = len(order)
+    W, _, _, _ = _host_smooth_knn(dist, n_neighbors)
+    rowptr, col, val = _host_fuzzy_graph(order, W)
+    A = np.zeros((N, N))
+    A[np.repeat(np.arange(N), np.diff(rowptr)), col] = val.astype(np.float64)
+    degree = A.sum(axis=1)
+    jsp.check_degree(degree)
+    if density_normalize:
+        inv = 1.0 / degree
+        degree = (A @ inv) * inv
+        jsp.check_degree(degree)
+        scale = inv / np.sqrt(degree)
+    else:
+        scale = 1.0 / np.sqrt(degree)
+    S = scale[:, None] * A * scale[None, :]
+    k = n_components + 1
+    w, V = np.linalg.eigh((S + S.T) / 2.0)
+    theta, Q = w[::-1][:k].copy(), np.ascontiguousarray(V[:, ::-1][:, :k])
+    resid = np.linalg.norm(S @ Q - Q * theta[None, :], axis=0)
+    graph = None
+    if return_graph:
+        from scipy.sparse import csr_matrix
+        graph = csr_matrix((val, col, rowptr), shape=(N, N))
+    return jsp.spectral_summary(Q, theta, resid, degree, n_cells, resid.max() <= tol, 0, 0, [], n_neighbors, len(col), kind, density_normalize, tol,
+                                graph)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):

@@ -11,7 +11,8 @@
 The kernels are in csrc/umap.hip (include/jamie_hip.h, "UMAP layout on the device").  The neighbours are `neighbors.self_knn`'s:
 n_neighbors - 1 <= 128 other cells per cell.  The definition (shared with the float64 host route of jamie.py) is DESIGN.md §20;
 it departs from umap-learn in four places: the epochs are synchronous (every read is from the layout the epoch started with),
-every firing draws exactly `negative_sample_rate` cells, sigma has a per-row floor, and the init is PCA, not spectral.
+every firing draws exactly `negative_sample_rate` cells, sigma has a per-row floor, and the init is PCA, not spectral (the
+spectral init is `spectral.spectral(...)['umap_init']`, passed as the array `init`: jamie_amd/spectral.py).
 """
 import numpy as np
 import torch
