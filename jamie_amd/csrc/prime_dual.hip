@@ -34,6 +34,9 @@ __global__ __launch_bounds__(256) void pd_update_kernel(PdUpdate p) {
     const int c0 = cb * PD_TC + lane * 4;
     const float a4 = 4.f * p.alpha[0];
     const float pho1 = 0.9f, pho2 = 0.999f, delta = 10e-8f;                    // jamie.py:347-349
+    // 1 - pho formed in double and rounded once, as the reference's python scalars are: 1.f - 0.999f is 1.3e-5 off 0.001, which
+    // put the first step 6.5e-6 off 1
+    const float q1 = (float)(1.0 - 0.9), q2 = (float)(1.0 - 0.999);
     const bool vec = (p.n & 3) == 0;
     float lam[4], cterm[4], csum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -68,8 +71,8 @@ __global__ __launch_bounds__(256) void pd_update_kernel(PdUpdate p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float grad = 4.f * g1[e] - a4 * g2[e] + rterm + lam[e] + p.rho * cterm[e];   // jamie.py:358-373
-                a[e] = pho1 * a[e] + (1.f - pho1) * grad;                                           // jamie.py:376-377
-                b[e] = pho2 * b[e] + (1.f - pho2) * grad * grad;
+                a[e] = pho1 * a[e] + q1 * grad;                                                     // jamie.py:376-377
+                b[e] = pho2 * b[e] + q2 * grad * grad;
                 const float step = (a[e] / p.d1) / (sqrtf(b[e] / p.d2) + delta);                    // jamie.py:378-380
                 const float ft = fmaxf(f[e] - step, 0.f);                                           // jamie.py:381-382
                 f[e] = (1.f - p.epsilon) * f[e] + p.epsilon * ft;                                   // jamie.py:384
