@@ -807,6 +807,35 @@ int jamie_feature_auroc(const float* X, const float* Y, long long N, int d, cons
                         long long* U2, void* ws, long long ws_bytes, int last_stage, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Marker features on the device (jamie_amd/markers.py; scanpy's rank_genes_groups): one-vs-rest statistics of every feature for
+ * every group of cells.  X is fp32 [N, d] row-major and finite, 2 <= N <= 2^21 = 2097152: with every value of a feature tied the tie
+ * term is N^3 - N, which that bound keeps below 2^63, and twice a rank stays within 32 bits.  The cells are visited in group
+ * order and X is not permuted: order[N] (int32) is a stable argsort of the cells' group codes, codes[N] (int32) the codes in that
+ * order (ascending, in [0, G)), seg_off[G + 1] (int32) where each group's cells start in it.  All three live on the device; an
+ * entry of `order` outside [0, N) or a code outside [0, G) is skipped.  Deterministic: integer atomics and fp64 sums in a fixed
+ * order only; bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` (host arithmetic only, no device needed).  which = 0: jamie_group_moments on [N, d] with G groups: fp64 partials
+ * [N / 512 + G, d, 2].  which = 1: jamie_group_rank_sums on a group of d features of N cells: two uint32 key buffers [d, Npad], Npad
+ * = N rounded up to a multiple of 4096.  0 for any other `which`, N, d or G < 1 or N > 2^21 */
+long long jamie_markers_workspace(long long N, int d, int G, int which);
+/* For the features f in [f0, f0 + dg), 1 <= dg <= 32768, with lb = #{cells j : X[j, f] < X[i, f]} and ub = #{cells j : X[j, f] <=
+ * X[i, f]} of cell i: R2[f * G + g] = sum over the cells of group g of (lb + ub + 1), twice the sum of their midranks among all N
+ * cells, and tie[f] = sum over all cells of ((ub - lb)^2 - 1) = sum over the tie groups of (t^3 - t).  int64, R2 [d, G] and tie [d],
+ * entries outside the feature group untouched.  Values compare as floats (-0.0 == +0.0).  last_stage = 4; 1 .. 3 stop after the
+ * key pass, the chunk sort, the merge passes and leave the keys in `ws` (first buffer after an even number of merge passes, else
+ * the second): R2 and tie are then zero */
+int jamie_group_rank_sums(const float* X, long long N, int d, const int32_t* order, const int32_t* codes, int G, int f0, int dg,
+                          long long* R2, long long* tie, void* ws, long long ws_bytes, int last_stage, void* stream);
+/* sums[(g * d + f) * 2 + q], fp64 [G, d, 2]: over the cells i of group g, q = 0 the sum of dx = (double)X[i, f] - (double)X[0, f],
+ * q = 1 the sum of dx^2.  A group's segment is cut into pieces of 512 cells; piece_off[G + 1] (int32, device) counts the pieces of
+ * the groups before each one, n_pieces = piece_off[G] <= N / 512 + G.  Within a piece cell m goes to row group m mod 16, a row group
+ * adds its cells in order, the 16 row groups are added in order, and a group's pieces are added in ascending order.  d <= 65535 * 64;
+ * `sums` is 16-byte aligned */
+int jamie_group_moments(const float* X, long long N, int d, const int32_t* order, const int32_t* seg_off, const int32_t* piece_off,
+                        int G, long long n_pieces, double* sums, void* ws, long long ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sparse cell matrices (jamie_amd/sparse_input.py): `preclass(sample, axis=0)` of the reference (utilities.py:654-678; built at
  * jamie.py:462-465, applied at jamie.py:508 to the fitting sample and at jamie.py:806-837 to new cells in modal_predict /
  * transform / transform_one) for a scipy CSR matrix of N cells x d features, without a dense copy of the input on the host or the

@@ -265,6 +265,11 @@ EXPORTS = {
                                       C.c_void_p]),
     'jamie_feature_auroc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    'jamie_markers_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    'jamie_group_rank_sums': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    'jamie_group_moments': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
+                                      C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     'jamie_sparse_workspace': (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
     'jamie_csc_col_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
@@ -963,6 +968,23 @@ def feature_stats(X, Y, r, mse, ws):
 def feature_auroc(X, Y, thr, f0, dg, n_pos, U2, ws, last_stage=4):
     _call('jamie_feature_auroc', ptr(X), ptr(Y), X.shape[0], X.shape[1], ptr(thr), int(f0), int(dg), ptr(n_pos), ptr(U2), ptr(ws),
           ws.numel() * ws.element_size(), int(last_stage), _stream())
+
+
+# ---- marker features (jamie_amd/markers.py; include/jamie_hip.h "Marker features on the device") ----
+def markers_workspace(N, d, G, which):
+    """Bytes of workspace: which = 0 for group_moments on [N, d] with G groups, 1 for group_rank_sums on a group of d features.
+    Host arithmetic."""
+    return int(load().jamie_markers_workspace(int(N), int(d), int(G), int(which)))
+
+
+def group_rank_sums(X, order, codes, G, f0, dg, R2, tie, ws, last_stage=4):
+    _call('jamie_group_rank_sums', ptr(X), X.shape[0], X.shape[1], ptr(order), ptr(codes), int(G), int(f0), int(dg), ptr(R2), ptr(tie),
+          ptr(ws), ws.numel() * ws.element_size(), int(last_stage), _stream())
+
+
+def group_moments(X, order, seg_off, piece_off, G, n_pieces, sums, ws):
+    _call('jamie_group_moments', ptr(X), X.shape[0], X.shape[1], ptr(order), ptr(seg_off), ptr(piece_off), int(G), int(n_pieces),
+          ptr(sums), ptr(ws), ws.numel() * ws.element_size(), _stream())
 
 
 # ---- sparse cell matrices (jamie_amd/sparse_input.py; include/jamie_hip.h "Sparse cell matrices") ----

@@ -21,7 +21,7 @@ import torch
 from . import _native as nv
 from .metrics import _device_input
 
-CHUNK = 4096            # keys one workgroup sorts in LDS (csrc/imputation.hip): runs start at this length, N is padded to it
+CHUNK = 4096            # keys one workgroup sorts in LDS (csrc/key_sort.h): runs start at this length, N is padded to it
 ROW_BLOCK = 512         # rows per workgroup of the moments pass
 MAX_GROUP = 32768       # features per launch
 

@@ -81,7 +81,9 @@ class JAMIE:
                    2N x 2N distance matrix: a few thousand cells at most); 'device': on the MI355X (jamie_amd/metrics.py)
                    in fp32 without any N x N matrix, euclidean only, for whole data sets.  `test_imputation` (per-feature
                    correlation, MSE and AUROC of imputed against measured values): 'host' float64 numpy and sklearn
-                   `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts).  `test_silhouette`
+                   `roc_auc_score`, 'device' jamie_amd/imputation.py (fp64 sums, exact integer rank counts).  `rank_features`
+                   (marker features of every group against the rest: Wilcoxon rank sums, Welch's t): 'host' float64 numpy with
+                   `scipy.stats.rankdata`, 'device' jamie_amd/markers.py (exact integer rank sums, fp64 moments).  `test_silhouette`
                    (silhouette widths of the pooled cells by label, and by modality within every label; needs no paired cells):
                    'host' sklearn `silhouette_samples` on the N x N distances in float64, 'device' jamie_amd/metrics.py
                    `silhouette` (fp32 distances summed per cell and class in fp64, no N x N matrix).  `test_lisi` (iLISI over the
@@ -1144,6 +1146,27 @@ class JAMIE:
             print(f'imputation {name}: {mean}')
         return out
 
+    def rank_features(self, data, labels, n_top=25, tie_correct=True, max_workspace=1 << 30):
+        """Which features mark each group (scanpy's `rank_genes_groups`): every group of `labels` (cluster ids of
+        `test_clustering`, or cell types) against the rest, for each feature of `data` [cells, features] -- measured values or
+        what `modal_predict` imputes.  The dict of jamie_amd/markers.py `rank_features`: exact Wilcoxon rank sums (`rank_sum2`,
+        `tie_term`, `U2`) with `auroc`, `z`, `pvals`, `pvals_adj`; `mean`, `var` and Welch's `t`, `t_df`, `t_pvals` of group
+        against rest; `logfoldchanges` (assumes log1p data), `mean_difference`; `ranking` [groups, n_top] by descending `z`.  NaN
+        where a statistic is undefined: a single group, a constant feature (`z`), fewer than 2 cells on a side (`var`, `t`).  At
+        most 2^21 cells.  metrics='host': float64 numpy with `scipy.stats.rankdata` per feature; metrics='device':
+        jamie_amd/markers.py (fp32 values, exact integer rank sums, fp64 moments)."""
+        from . import markers as jmk
+        N, d, labels, n_top = jmk.check_rank_features(data, labels, n_top)
+        if self.metrics == 'device':
+            out = jmk.rank_features(data, labels, n_top=n_top, tie_correct=tie_correct, max_workspace=max_workspace,
+                                    device=self.device)
+        else:
+            out = _host_rank_features(data.toarray() if hasattr(data, 'toarray') else _host_array(data), labels, n_top, tie_correct)
+        z = np.abs(out['z'])
+        print(f"rank_features: {len(out['groups'])} groups, {d} features, largest |z| "
+              f"{float(np.nanmax(z)) if np.any(~np.isnan(z)) else float('nan')}")
+        return out
+
 
 def _host_array(x):
     return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
@@ -1551,3 +1574,26 @@ def _host_imputation_metrics(imputed, measured, threshold):
         if 0 < label.sum() < N:
             auroc[f] = roc_auc_score(label, X[:, f])
     return {'correlation': r, 'mse': ((X - Y) ** 2).mean(0), 'auroc': auroc}
+
+
+def _host_rank_features(data, labels, n_top, tie_correct):
+    """The dict of `markers.rank_features` in float64 numpy: midranks from `scipy.stats.rankdata` per feature, tie groups from
+    `np.unique`, the same shifted sums as the device (pivot: row 0), finished by `markers.finish`."""
+    from scipy.stats import rankdata
+    from . import markers as jmk
+    X = np.asarray(data, dtype=np.float64)
+    N, d, labels, n_top = jmk.check_rank_features(X, labels, n_top)
+    if not np.isfinite(X).all():
+        raise ValueError('rank_features: input contains NaN or infinity')
+    lay = jmk.group_layout(labels)
+    starts = lay['seg_off'][:-1].astype(np.int64)
+    Xs = X[lay['order']]                                                      # the cells in group order
+    ranks2 = np.rint(2.0 * rankdata(Xs, axis=0)).astype(np.int64)            # (a midrank is a multiple of 1/2)
+    rank_sum2 = np.add.reduceat(ranks2, starts, axis=0)
+    tie_term = np.empty(d, np.int64)
+    for f in range(d):
+        t = np.unique(X[:, f], return_counts=True)[1].astype(object)          # (Python integers: t^3 up to 2^63)
+        tie_term[f] = int((t ** 3 - t).sum())
+    dx = Xs - X[0]
+    sums = np.stack([np.add.reduceat(dx, starts, axis=0), np.add.reduceat(dx * dx, starts, axis=0)], axis=2)
+    return jmk.finish(lay['groups'], lay['n'], rank_sum2, tie_term, X[0], sums, n_top, tie_correct)
