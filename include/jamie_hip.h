@@ -403,7 +403,7 @@ int jamie_sample_indices(int32_t* idx, int B, long long N, long long offset, int
 int jamie_sample_indices_group(const jamie_sample_args* list /*host*/, int count, const uint64_t* rng, void* stream);
 /* 'hybrid' sampler of partial-correspondence training on the device (jamie.py:559-573, corrected): slot b is, with
  * probability true_ratio, known pair pairs[pidx[b] % num_corr] = (row of modality 0, row of modality 1), else (r0[b], r1[b]);
- * pidx / r0 / r1: candidate draws from jamie_sample_indices */
+ * true_ratio = 1 pairs every slot; pidx / r0 / r1: candidate draws from jamie_sample_indices */
 int jamie_hybrid_assemble(const int32_t* pairs /*[num_corr,2]*/, const int32_t* pidx, const int32_t* r0, const int32_t* r1,
                           int B, int num_corr, float true_ratio, const uint64_t* rng, int rng_stream, int32_t* idx0,
                           int32_t* idx1, void* stream);

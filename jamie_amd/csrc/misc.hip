@@ -251,13 +251,16 @@ __global__ __launch_bounds__(256) void col_moment_kernel(const T* __restrict__ X
     if (rp == 0 && col < d) partials[(long long)blockIdx.y * d + col] = (sh[0][c] + sh[1][c]) + (sh[2][c] + sh[3][c]);
 }
 
-__global__ __launch_bounds__(256) void col_moment_finish_kernel(const double* partials, int R, int d, double inv_n,
+__global__ __launch_bounds__(256) void col_moment_finish_kernel(const double* partials, int R, int d, double n,
                                                                 int take_sqrt, double* out) {
     const int col = blockIdx.x * 256 + threadIdx.x;
     if (col >= d) return;
     double s = 0.0;
     for (int r = 0; r < R; ++r) s += partials[(long long)r * d + col];
-    s *= inv_n;
+    // sum / N as numpy forms it, not sum * (1 / N): a constant feature c has the sum c N exactly, c N / N is c, every
+    // deviation is 0 and the feature standardises to 0 / 0 -> NaN -> 0 as in the reference, while fl(c N * fl(1 / N)) is
+    // one ulp off c for one N in eight (N = 49 is the first) and the feature came out as +-1
+    s /= n;
     out[col] = take_sqrt ? sqrt(s) : s;
 }
 
@@ -284,7 +287,7 @@ extern "C" int jamie_col_stats(const void* X, int is_f64, long long N, int d, lo
         const double* mu = pass ? mean : nullptr;
         if (is_f64) hipLaunchKernelGGL(col_moment_kernel<double>, grid, dim3(256), 0, st, (const double*)X, N, d, ld, mu, partials);
         else hipLaunchKernelGGL(col_moment_kernel<float>, grid, dim3(256), 0, st, (const float*)X, N, d, ld, mu, partials);
-        hipLaunchKernelGGL(col_moment_finish_kernel, fin, dim3(256), 0, st, partials, n_row_blocks, d, 1.0 / (double)N, pass,
+        hipLaunchKernelGGL(col_moment_finish_kernel, fin, dim3(256), 0, st, partials, n_row_blocks, d, (double)N, pass,
                            pass ? sd : mean);
     }
     return jamie_launch_status("jamie_col_stats");
@@ -315,7 +318,9 @@ __global__ __launch_bounds__(256) void hybrid_assemble_kernel(const int32_t* __r
     if (b >= B) return;
     const Philox4 u = jamie_rand4(rng, (uint32_t)rng_stream, (uint64_t)b);
     const float x = (float)u.v[0] * 2.3283064365386963e-10f;
-    const bool paired = num_corr > 0 && x < true_ratio;
+    // (float)v rounds to nearest: v >= 0xFFFFFF80 gives x = 1.0, which `x < 1` would leave unpaired where the reference's
+    // `np.random.rand() < 1` pairs every slot
+    const bool paired = num_corr > 0 && (x < true_ratio || true_ratio >= 1.f);
     if (paired) {
         const int k = pidx[b] % num_corr;
         idx0[b] = pairs[2 * k];
