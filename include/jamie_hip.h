@@ -836,6 +836,47 @@ int jamie_group_moments(const float* X, long long N, int d, const int32_t* order
                         int G, long long n_pieces, double* sums, void* ws, long long ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Louvain communities on the device (jamie_amd/louvain.py): one level of modularity optimisation on an integer
+ * level graph of n < 2^31 nodes in CSR: rowptr[n + 1] (int64), col[nnz] (int32, never the row itself), w[nnz] (int64 >= 1),
+ * loop[n] (int64 >= 0), k[n] = the row's weights + its loop, two_m = sum k < 2^52.  The state of a level is comm[n] (int32, the
+ * community of every node, in [0, n)), tot[n] (int64, the k of a community's members) and size[n] (int32, their number).  All
+ * arrays live on the device.  Every sum of weights is an int64 sum and the only atomics are integer ones, so every result is the
+ * same bits from run to run and equals a restatement in any order.  Row extents are clamped to [0, nnz]; a column or a
+ * community outside [0, n) is skipped.
+ * ------------------------------------------------------------------------------------------------ */
+/* w[e] = max(1, rint((double)val[e] * 2^20)) (round half to even) for the nnz entries of an fp32 CSR graph, k[i] = the sum of
+ * row i's w */
+int jamie_louvain_quantise(const long long* rowptr, const float* val, long long nnz, long long n, long long* w, long long* k,
+                           void* stream);
+/* bytes of `ws` for jamie_louvain_move on `count` rows beyond the LDS cap whose lengths are the HOST array lens[count] (host
+ * arithmetic only, no device needed): 12 bytes per slot, a row of len entries owning the power of two from 2 len + 2 up.  0 for a
+ * null pointer, count < 1 or a length outside [0, 2^31) */
+long long jamie_louvain_workspace(const long long* lens, long long count);
+/* target[i] for the nodes i of nodes[n_short + n_long + n_global] (int32, distinct), from comm, tot and size as they stand; the
+ * entries of `target` of other nodes are not touched and `comm` is not written (`target` must be another array).  With c =
+ * comm[i], kid = the w of row i's entries whose column is in community d, T_d = tot[d] (less k[i] for d = c):
+ *     gain(d) = (double)kid - ((gamma * (double)k[i]) * (double)T_d) / (double)two_m        (fp64, this order, no contraction)
+ * and target[i] is the community d of a stored neighbour with the largest gain(d) > gain(c), the lowest d among equal gains, c
+ * when there is none.  When size[c] == 1 a community d > c with size[d] == 1 is not admitted.  The list holds first the n_short
+ * nodes whose rows have at most 64 entries (a wave each), then the n_long ones with at most 2048 (a workgroup each, the
+ * candidates in LDS), then the n_global longer ones: row r of those owns the slots [slot_off[r], slot_off[r + 1]) of `ws`
+ * (slot_off int64 [n_global + 1] on the device, n_slots = slot_off[n_global], ws_bytes >= 12 n_slots, 8-byte aligned).  A node
+ * whose row does not fit its part of the list, whose community is outside [0, n) or whose slots are too few keeps target = comm
+ * and sets bit 0, 1 or 2 of *flag (int32 on the device, never cleared here) */
+int jamie_louvain_move(const long long* rowptr, const int32_t* col, const long long* w, long long nnz, long long n,
+                       const long long* k, const int32_t* comm, const long long* tot, const int32_t* size, double gamma,
+                       long long two_m, const int32_t* nodes, long long n_short, long long n_long, long long n_global,
+                       const long long* slot_off, long long n_slots, void* ws, long long ws_bytes, int32_t* target, int32_t* flag,
+                       void* stream);
+/* for the `count` distinct nodes i of `nodes` with target[i] != comm[i]: comm[i] = target[i], tot and size of the two
+ * communities adjusted by k[i] and 1 (integer atomics), *moved (int64 on the device) grown by one */
+int jamie_louvain_apply(const int32_t* nodes, long long count, const int32_t* target, const long long* k, int32_t* comm,
+                        long long* tot, int32_t* size, long long* moved, long long n, void* stream);
+/* inside[c] (int64 [n], zeroed here) = the w of the stored entries with both ends in community c, plus the loops of its nodes */
+int jamie_louvain_internal(const long long* rowptr, const int32_t* col, const long long* w, long long nnz, long long n,
+                           const long long* loop, const int32_t* comm, long long* inside, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sparse cell matrices (jamie_amd/sparse_input.py): `preclass(sample, axis=0)` of the reference (utilities.py:654-678; built at
  * jamie.py:462-465, applied at jamie.py:508 to the fitting sample and at jamie.py:806-837 to new cells in modal_predict /
  * transform / transform_one) for a scipy CSR matrix of N cells x d features, without a dense copy of the input on the host or the

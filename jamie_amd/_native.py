@@ -270,6 +270,15 @@ EXPORTS = {
                                         C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     'jamie_group_moments': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong,
                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'jamie_louvain_quantise': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_louvain_workspace': (C.c_longlong, [C.c_void_p, C.c_longlong]),
+    'jamie_louvain_move': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_double, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong,
+                                     C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_louvain_apply': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_longlong, C.c_void_p]),
+    'jamie_louvain_internal': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     'jamie_sparse_workspace': (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
     'jamie_csc_col_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
@@ -985,6 +994,35 @@ def group_rank_sums(X, order, codes, G, f0, dg, R2, tie, ws, last_stage=4):
 def group_moments(X, order, seg_off, piece_off, G, n_pieces, sums, ws):
     _call('jamie_group_moments', ptr(X), X.shape[0], X.shape[1], ptr(order), ptr(seg_off), ptr(piece_off), int(G), int(n_pieces),
           ptr(sums), ptr(ws), ws.numel() * ws.element_size(), _stream())
+
+
+# ---- Louvain communities (jamie_amd/louvain.py; include/jamie_hip.h "Louvain communities on the device") ----
+def louvain_quantise(rowptr, val, w, k):
+    _call('jamie_louvain_quantise', ptr(rowptr), ptr(val), int(val.numel()), k.shape[0], ptr(w), ptr(k), _stream())
+
+
+def louvain_workspace(lens):
+    """Bytes of workspace for louvain_move on rows beyond the LDS cap of these lengths (a host array).  Host arithmetic."""
+    lens = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+    return int(load().jamie_louvain_workspace(lens.ctypes.data, len(lens)))
+
+
+def louvain_move(rowptr, col, w, k, comm, tot, size, gamma, two_m, nodes, counts, slot_off, ws, target, flag):
+    """`nodes`: the list from its first short row on; counts = (short, long, global); slot_off int64 [global + 1] or None."""
+    n_slots = int(slot_off[-1].item()) if counts[2] else 0
+    _call('jamie_louvain_move', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), k.shape[0], ptr(k), ptr(comm), ptr(tot), ptr(size),
+          float(gamma), int(two_m), ptr(nodes), int(counts[0]), int(counts[1]), int(counts[2]), ptr(slot_off), n_slots, ptr(ws),
+          ws.numel() * ws.element_size(), ptr(target), ptr(flag), _stream())
+
+
+def louvain_apply(nodes, target, k, comm, tot, size, moved):
+    _call('jamie_louvain_apply', ptr(nodes), int(nodes.numel()), ptr(target), ptr(k), ptr(comm), ptr(tot), ptr(size), ptr(moved),
+          k.shape[0], _stream())
+
+
+def louvain_internal(rowptr, col, w, loop, comm, inside):
+    _call('jamie_louvain_internal', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), loop.shape[0], ptr(loop), ptr(comm), ptr(inside),
+          _stream())
 
 
 # ---- sparse cell matrices (jamie_amd/sparse_input.py; include/jamie_hip.h "Sparse cell matrices") ----

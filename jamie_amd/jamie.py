@@ -1129,6 +1129,27 @@ class JAMIE:
               f"{out['residuals'].max():.2e}, {out['applies']} applies")
         return out
 
+    def louvain(self, integrated_data, datatype=None, resolution=1.0, n_neighbors=15, max_levels=20, max_sweeps=32, tol=1e-7,
+                return_graph=False):
+        """Louvain communities of the pooled embeddings (scanpy's `tl.louvain`): multi-level modularity
+        optimisation of the fuzzy graph of `umap` at `resolution`, with the weights as integers (val 2^20, rounded), so that every
+        sum is exact and the result is the same bits on every run and on both routes for one graph.  `clusters` (int32 ids by
+        descending size, one array per embedding: usable as `rank_features(..., labels=)`), `n_clusters`, `sizes`, `modularity`,
+        `levels` (per accepted level: nodes, communities, sweeps, the moved count per sweep, modularity, two_m),
+        `modality_contingency` [clusters, M] and, with labels, `ari`, `nmi`, `contingency` and the `labels` in `np.unique` order
+        (each None without labels), `n_neighbors`, `n_edges` and `graph` (scipy CSR with `return_graph`).  No refinement step
+        (Leiden) and no splitting of disconnected communities.  metrics='host': int64 / float64 numpy on N x N distances, for a
+        few thousand cells; metrics='device': jamie_amd/louvain.py `louvain`."""
+        from . import louvain as jlv
+        checked = jlv.check_louvain(integrated_data, datatype, resolution, n_neighbors, max_levels, max_sweeps, tol, 'louvain')
+        if self.metrics == 'device':
+            out = jlv.louvain_checked(integrated_data, datatype, *checked, return_graph, self.device)
+        else:
+            out = _host_louvain([_host_array(e) for e in integrated_data], datatype, *checked, return_graph)
+        print(f"louvain: {out['n_clusters']} clusters over {len(out['levels'])} levels, modularity {out['modularity']:.6f}, ARI "
+              f"{out['ari']}")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1486,6 +1507,132 @@ def _host_spectral(embeddings, n_components, n_neighbors, kind, density_normaliz
         graph = csr_matrix((val, col, rowptr), shape=(N, N))
     return jsp.spectral_summary(Q, theta, resid, degree, n_cells, resid.max() <= tol, 0, 0, [], n_neighbors, len(col), kind, density_normalize, tol,
                                 graph)
+
+
+def _host_louvain_move(rowptr, col, w, k, comm, tot, size, nodes, gamma, two_m):
+    """The targets of `nodes` (int64 ids) from comm, tot and size as they stand, all rows at once: the
+    entries are sorted by (node, community), summed per pair in int64 and the admitted pairs ordered by (node, gain descending,
+    community ascending)."""
+    lens = rowptr[nodes + 1] - rowptr[nodes]
+    r = np.repeat(np.arange(len(nodes)), lens)
+    e = np.repeat(rowptr[nodes] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()))
+    c = comm[nodes]
+    d, we = comm[col[e]], w[e]
+    own = d == c[r]
+    kic = np.zeros(len(nodes), np.int64)
+    np.add.at(kic, r[own], we[own])
+    ki = k[nodes]
+    gki = gamma * ki.astype(np.float64)
+    m2 = float(two_m)
+    gain_c = kic.astype(np.float64) - (gki * (tot[c] - ki).astype(np.float64)) / m2
+    target = c.copy()
+    ro, do, wo = r[~own], d[~own], we[~own]
+    if len(ro):
+        order = np.lexsort((do, ro))
+        ro, do, wo = ro[order], do[order], wo[order]
+        starts = np.nonzero(np.concatenate([[True], (ro[1:] != ro[:-1]) | (do[1:] != do[:-1])]))[0]
+        kid, rg, dg = np.add.reduceat(wo, starts), ro[starts], do[starts]
+        gain = kid.astype(np.float64) - (gki[rg] * tot[dg].astype(np.float64)) / m2
+        ok = (gain > gain_c[rg]) & ~((size[c[rg]] == 1) & (size[dg] == 1) & (dg > c[rg]))
+        rg, dg, gain = rg[ok], dg[ok], gain[ok]
+        if len(rg):
+            best = np.lexsort((dg, -gain, rg))
+            rg, dg = rg[best], dg[best]
+            head = np.concatenate([[True], rg[1:] != rg[:-1]])
+            target[rg[head]] = dg[head]
+    return target
+
+
+def _host_louvain_levels(rowptr, col, w, loop, resolution=1.0, max_levels=20, max_sweeps=32, tol=1e-7):
+    """DESIGN.md §23 on an integer level graph (rowptr, col, w int64, loop int64) in numpy: dict(comm int64 [n] the composed map
+    of the accepted levels, modularity, levels)."""
+    from . import louvain as jlv
+    rowptr, col = np.asarray(rowptr, np.int64), np.asarray(col, np.int64)
+    w, loop = np.asarray(w, np.int64), np.asarray(loop, np.int64)
+    n = len(loop)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    k = loop.copy()
+    np.add.at(k, row, w)
+    two_m = int(k.sum())
+    jlv.check_totals(n, two_m)
+    q_prev = jlv.modularity_from_tables(loop, k, two_m, resolution)
+    result = np.arange(n)
+    levels = []
+    while len(levels) < max_levels:
+        n = len(loop)
+        cls = jlv.node_class(np.arange(n))
+        lists = [np.nonzero(cls == s)[0] for s in range(jlv.CLASSES)]
+        comm, tot, size = np.arange(n), k.copy(), np.ones(n, np.int64)
+        history = []
+        for _ in range(max_sweeps):
+            moved = 0
+            for nodes in lists:
+                if not len(nodes):
+                    continue
+                target = _host_louvain_move(rowptr, col, w, k, comm, tot, size, nodes, resolution, two_m)
+                mv = target != comm[nodes]
+                i, c, d = nodes[mv], comm[nodes][mv], target[mv]
+                np.subtract.at(tot, c, k[i])
+                np.add.at(tot, d, k[i])
+                np.subtract.at(size, c, 1)
+                np.add.at(size, d, 1)
+                comm[i] = d
+                moved += int(mv.sum())
+            history.append(moved)
+            if moved == 0 or jlv.stalled(history):
+                break
+        inside_e = comm[row] == comm[col]
+        inside = np.zeros(n, np.int64)
+        np.add.at(inside, comm, loop)
+        np.add.at(inside, comm[row][inside_e], w[inside_e])
+        q = jlv.modularity_from_tables(inside, tot, two_m, resolution)
+        if not q > q_prev + tol:
+            break
+        ids, cmap = np.unique(comm, return_inverse=True)
+        cmap = cmap.reshape(-1)
+        nc = len(ids)
+        crow, ccol = cmap[row], cmap[col]
+        new_loop = np.zeros(nc, np.int64)
+        np.add.at(new_loop, cmap, loop)
+        np.add.at(new_loop, crow[inside_e], w[inside_e])
+        keys, inv = np.unique(crow[~inside_e] * nc + ccol[~inside_e], return_inverse=True)
+        new_w = np.zeros(len(keys), np.int64)
+        np.add.at(new_w, inv.reshape(-1), w[~inside_e])
+        new_k = np.zeros(nc, np.int64)
+        np.add.at(new_k, cmap, k)
+        rowptr = np.concatenate([[0], np.cumsum(np.bincount(keys // nc, minlength=nc))]).astype(np.int64)
+        col, w, loop, k = keys % nc, new_w, new_loop, new_k
+        row = np.repeat(np.arange(nc), np.diff(rowptr))
+        levels.append(jlv.level_record(n, nc, history, q, int(k.sum())))
+        result = cmap[result]
+        q_prev = q
+    return dict(comm=result, modularity=q_prev, levels=levels)
+
+
+def _host_louvain_graph(rowptr, col, val, resolution=1.0, max_levels=20, max_sweeps=32, tol=1e-7):
+    """`louvain.communities` in numpy on the CSR arrays of any fp32 graph: dict(clusters int32 [N], sizes, modularity, levels)."""
+    from . import louvain as jlv
+    n = len(rowptr) - 1
+    out = _host_louvain_levels(rowptr, col, jlv.quantise(val), np.zeros(n, np.int64), resolution, max_levels, max_sweeps, tol)
+    clusters, sizes = jlv.relabel(out['comm'])
+    return dict(clusters=clusters, sizes=sizes, modularity=out['modularity'], levels=out['levels'])
+
+
+def _host_louvain(embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol, return_graph=False):
+    """The dict of `louvain.louvain` in int64 / float64 numpy on `_host_fuzzy_graph`'s graph: the same definition."""
+    from . import louvain as jlv
+    n_cells = [e.shape[0] for e in embeddings]
+    order, dist = _host_sorted_neighbors(embeddings, n_neighbors - 1, 'louvain')
+    W, _, _, _ = _host_smooth_knn(dist, n_neighbors)
+    rowptr, col, val = _host_fuzzy_graph(order, W)
+    out = _host_louvain_graph(rowptr, col, val, resolution, max_levels, max_sweeps, tol)
+    table_mod, table_lab, classes = jlv.host_tables(out['clusters'], n_cells, labels, len(out['sizes']))
+    graph = None
+    if return_graph:
+        from scipy.sparse import csr_matrix
+        graph = csr_matrix((val, col, rowptr), shape=(len(order), len(order)))
+    return jlv.louvain_summary(out['clusters'], out['sizes'], out['modularity'], out['levels'], n_cells, table_mod, table_lab, classes,
+                               resolution, n_neighbors, len(col), graph)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
