@@ -877,6 +877,39 @@ int jamie_louvain_internal(const long long* rowptr, const int32_t* col, const lo
                            const long long* loop, const int32_t* comm, long long* inside, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Leiden communities on the device (jamie_amd/leiden.py): the refinement step of one level, on the level graph,
+ * the communities comm[n] and their totals tot[n] of "Louvain communities on the device" above.  The state of a refinement is
+ * ref[n] (int32, the sub-community of every node, named after its founder: a non-empty sub-community s holds node s), rtot[n]
+ * (int64, the k of its members), rsize[n] (int32, their number) and cut[n] (int64, below).  Only a node that is alone (ref[i] =
+ * i, rsize[i] = 1) ever moves, so a sub-community never loses a member.  With T = tot[comm[i]],
+ *     wc(x, t) := (double)x >= ((gamma * (double)t) * (double)(T - t)) / (double)two_m       (fp64, this order, no contraction)
+ * Every sum of weights is an int64 sum and the only atomics are integer ones: the same bits from run to run, equal to a
+ * restatement in any order.  Row extents are clamped to [0, nnz]; a column or a sub-community outside [0, n) is skipped.
+ * ------------------------------------------------------------------------------------------------ */
+/* cut[ref[i]] += the w of row i's entries (i, j) with comm[j] = comm[i] and ref[j] != ref[i], one integer atomic per row; the
+ * caller has zeroed cut[n] */
+int jamie_leiden_cut(const long long* rowptr, const int32_t* col, const long long* w, long long nnz, long long n, const int32_t* comm,
+                     const int32_t* ref, long long* cut, void* stream);
+/* target[i] for the nodes i of nodes[n_short + n_long + n_global] (one class; the list, the three bins, slot_off, ws and *flag as
+ * jamie_louvain_move), from the state as it stands; the entries of `target` of other nodes are not touched, and ref and comm are
+ * not written (`target` must be another array).  A node that is no longer alone gets target[i] = ref[i] at once.  For an alone
+ * node, with c = comm[i] and cut_i = the w of row i's entries inside c: target[i] = i unless wc(cut_i, k[i]); the candidates are
+ * the s = ref[j] of the stored neighbours j inside c, kis = the w of row i's entries whose column is in s; s is admitted unless
+ * rsize[s] = 1 and s > i, and only if wc(cut[s], rtot[s]) and
+ *     gain(s) = (double)kis - ((gamma * (double)k[i]) * (double)rtot[s]) / (double)two_m > 0
+ * and target[i] is the admitted s of the largest gain, the lowest s among equal gains, i when there is none */
+int jamie_leiden_refine(const long long* rowptr, const int32_t* col, const long long* w, long long nnz, long long n,
+                        const long long* k, const int32_t* comm, const long long* tot, const int32_t* ref, const long long* rtot,
+                        const int32_t* rsize, const long long* cut, double gamma, long long two_m, const int32_t* nodes,
+                        long long n_short, long long n_long, long long n_global, const long long* slot_off, long long n_slots,
+                        void* ws, long long ws_bytes, int32_t* target, int32_t* flag, void* stream);
+/* for the `count` distinct nodes i of `nodes` with s = target[i] != ref[i]: when target[s] != s (s's founder is itself leaving)
+ * the move is cancelled and counts[1] grows by one; otherwise ref[i] = s, rtot and rsize of the two sub-communities are adjusted
+ * by k[i] and 1 (integer atomics) and counts[0] grows by one.  counts is int64 [2] on the device; `target` is only read */
+int jamie_leiden_apply(const int32_t* nodes, long long count, const int32_t* target, const long long* k, int32_t* ref,
+                       long long* rtot, int32_t* rsize, long long* counts, long long n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sparse cell matrices (jamie_amd/sparse_input.py): `preclass(sample, axis=0)` of the reference (utilities.py:654-678; built at
  * jamie.py:462-465, applied at jamie.py:508 to the fitting sample and at jamie.py:806-837 to new cells in modal_predict /
  * transform / transform_one) for a scipy CSR matrix of N cells x d features, without a dense copy of the input on the host or the

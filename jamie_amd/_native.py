@@ -279,6 +279,14 @@ EXPORTS = {
                                       C.c_longlong, C.c_void_p]),
     'jamie_louvain_internal': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    'jamie_leiden_cut': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    'jamie_leiden_refine': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_longlong, C.c_void_p,
+                                      C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    'jamie_leiden_apply': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_longlong, C.c_void_p]),
     'jamie_sparse_workspace': (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
     'jamie_csc_col_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
@@ -1023,6 +1031,26 @@ def louvain_apply(nodes, target, k, comm, tot, size, moved):
 def louvain_internal(rowptr, col, w, loop, comm, inside):
     _call('jamie_louvain_internal', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), loop.shape[0], ptr(loop), ptr(comm), ptr(inside),
           _stream())
+
+
+# ---- Leiden communities (jamie_amd/leiden.py; include/jamie_hip.h "Leiden communities on the device") ----
+def leiden_cut(rowptr, col, w, comm, ref, cut):
+    """`cut` is zeroed here."""
+    cut.zero_()
+    _call('jamie_leiden_cut', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), comm.shape[0], ptr(comm), ptr(ref), ptr(cut), _stream())
+
+
+def leiden_refine(rowptr, col, w, k, comm, tot, ref, rtot, rsize, cut, gamma, two_m, nodes, counts, slot_off, ws, target, flag):
+    """`nodes`: the list from its first short row on; counts = (short, long, global); slot_off int64 [global + 1] or None."""
+    n_slots = int(slot_off[-1].item()) if counts[2] else 0
+    _call('jamie_leiden_refine', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), k.shape[0], ptr(k), ptr(comm), ptr(tot), ptr(ref),
+          ptr(rtot), ptr(rsize), ptr(cut), float(gamma), int(two_m), ptr(nodes), int(counts[0]), int(counts[1]), int(counts[2]),
+          ptr(slot_off), n_slots, ptr(ws), ws.numel() * ws.element_size(), ptr(target), ptr(flag), _stream())
+
+
+def leiden_apply(nodes, target, k, ref, rtot, rsize, counts):
+    _call('jamie_leiden_apply', ptr(nodes), int(nodes.numel()), ptr(target), ptr(k), ptr(ref), ptr(rtot), ptr(rsize), ptr(counts),
+          k.shape[0], _stream())
 
 
 # ---- sparse cell matrices (jamie_amd/sparse_input.py; include/jamie_hip.h "Sparse cell matrices") ----

@@ -1138,7 +1138,7 @@ class JAMIE:
         `levels` (per accepted level: nodes, communities, sweeps, the moved count per sweep, modularity, two_m),
         `modality_contingency` [clusters, M] and, with labels, `ari`, `nmi`, `contingency` and the `labels` in `np.unique` order
         (each None without labels), `n_neighbors`, `n_edges` and `graph` (scipy CSR with `return_graph`).  No refinement step
-        (Leiden) and no splitting of disconnected communities.  metrics='host': int64 / float64 numpy on N x N distances, for a
+        and no splitting of disconnected communities: that is `leiden`.  metrics='host': int64 / float64 numpy on N x N distances, for a
         few thousand cells; metrics='device': jamie_amd/louvain.py `louvain`."""
         from . import louvain as jlv
         checked = jlv.check_louvain(integrated_data, datatype, resolution, n_neighbors, max_levels, max_sweeps, tol, 'louvain')
@@ -1148,6 +1148,30 @@ class JAMIE:
             out = _host_louvain([_host_array(e) for e in integrated_data], datatype, *checked, return_graph)
         print(f"louvain: {out['n_clusters']} clusters over {len(out['levels'])} levels, modularity {out['modularity']:.6f}, ARI "
               f"{out['ari']}")
+        return out
+
+    def leiden(self, integrated_data, datatype=None, resolution=1.0, n_neighbors=15, max_levels=20, max_sweeps=32, tol=1e-7,
+               return_graph=False):
+        """Leiden communities of the pooled embeddings (scanpy's `tl.leiden`; Traag, Waltman and van Eck 2019):
+        per level Louvain's move phase on the integer fuzzy graph of `louvain`, then a refinement that splits every community
+        into connected parts (only a node still alone joins a part, and only one inside its own community), then aggregation by
+        the parts, each starting the next level in its community.  Deterministic: the merge takes the best part, not a random
+        one.  The dict of `louvain`, with `levels` holding per level nodes, communities, sweeps, the moved count per sweep,
+        modularity, refined (the parts: the next level's nodes), merged, cancelled and two_m (the last three None on a last level
+        that was not refined), and `stop`: 'singletons' (no two nodes of the last level share a community), 'stuck' (no part
+        would merge: the level's nodes are returned) or 'max_levels'.  Every returned community is connected in the graph unless
+        stop is 'max_levels'.  `tol` is accepted for parity with `louvain` and unused.  The same bits on every run and on both
+        routes for one graph.  metrics='host': int64 / float64 numpy on N x N distances, for a few thousand cells;
+        metrics='device': jamie_amd/leiden.py `leiden`."""
+        from . import louvain as jlv
+        checked = jlv.check_louvain(integrated_data, datatype, resolution, n_neighbors, max_levels, max_sweeps, tol, 'leiden')
+        if self.metrics == 'device':
+            from . import leiden as jld
+            out = jld.leiden_checked(integrated_data, datatype, *checked, return_graph, self.device)
+        else:
+            out = _host_leiden([_host_array(e) for e in integrated_data], datatype, *checked, return_graph)
+        print(f"leiden: {out['n_clusters']} clusters over {len(out['levels'])} levels ({out['stop']}), modularity "
+              f"{out['modularity']:.6f}, ARI {out['ari']}")
         return out
 
     def test_imputation(self, imputed, measured, threshold=0.0):
@@ -1543,6 +1567,60 @@ def _host_louvain_move(rowptr, col, w, k, comm, tot, size, nodes, gamma, two_m):
     return target
 
 
+def _host_louvain_sweeps(rowptr, col, w, k, comm, tot, size, gamma, two_m, max_sweeps):
+    """The sweeps of a level on comm, tot and size in place: the moved count of every sweep."""
+    from . import louvain as jlv
+    cls = jlv.node_class(np.arange(len(k)))
+    lists = [np.nonzero(cls == s)[0] for s in range(jlv.CLASSES)]
+    history = []
+    for _ in range(max_sweeps):
+        moved = 0
+        for nodes in lists:
+            if not len(nodes):
+                continue
+            target = _host_louvain_move(rowptr, col, w, k, comm, tot, size, nodes, gamma, two_m)
+            mv = target != comm[nodes]
+            i, c, d = nodes[mv], comm[nodes][mv], target[mv]
+            np.subtract.at(tot, c, k[i])
+            np.add.at(tot, d, k[i])
+            np.subtract.at(size, c, 1)
+            np.add.at(size, d, 1)
+            comm[i] = d
+            moved += int(mv.sum())
+        history.append(moved)
+        if moved == 0 or jlv.stalled(history):
+            break
+    return history
+
+
+def _host_louvain_inside(row, col, w, loop, comm):
+    """in_c int64 [n] and the mask of the stored entries with both ends in one community."""
+    inside_e = comm[row] == comm[col]
+    inside = np.zeros(len(loop), np.int64)
+    np.add.at(inside, comm, loop)
+    np.add.at(inside, comm[row][inside_e], w[inside_e])
+    return inside, inside_e
+
+
+def _host_louvain_aggregate(row, col, w, loop, k, comm):
+    """The next level's (rowptr, col, w, loop, k) and the new id of every node: communities renumbered in ascending id."""
+    ids, cmap = np.unique(comm, return_inverse=True)
+    cmap = cmap.reshape(-1)
+    nc = len(ids)
+    crow, ccol = cmap[row], cmap[col]
+    inside_e = crow == ccol
+    new_loop = np.zeros(nc, np.int64)
+    np.add.at(new_loop, cmap, loop)
+    np.add.at(new_loop, crow[inside_e], w[inside_e])
+    keys, inv = np.unique(crow[~inside_e] * nc + ccol[~inside_e], return_inverse=True)
+    new_w = np.zeros(len(keys), np.int64)
+    np.add.at(new_w, inv.reshape(-1), w[~inside_e])
+    new_k = np.zeros(nc, np.int64)
+    np.add.at(new_k, cmap, k)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(keys // nc, minlength=nc))]).astype(np.int64)
+    return rowptr, keys % nc, new_w, new_loop, new_k, cmap
+
+
 def _host_louvain_levels(rowptr, col, w, loop, resolution=1.0, max_levels=20, max_sweeps=32, tol=1e-7):
     """DESIGN.md §23 on an integer level graph (rowptr, col, w int64, loop int64) in numpy: dict(comm int64 [n] the composed map
     of the accepted levels, modularity, levels)."""
@@ -1560,50 +1638,15 @@ def _host_louvain_levels(rowptr, col, w, loop, resolution=1.0, max_levels=20, ma
     levels = []
     while len(levels) < max_levels:
         n = len(loop)
-        cls = jlv.node_class(np.arange(n))
-        lists = [np.nonzero(cls == s)[0] for s in range(jlv.CLASSES)]
         comm, tot, size = np.arange(n), k.copy(), np.ones(n, np.int64)
-        history = []
-        for _ in range(max_sweeps):
-            moved = 0
-            for nodes in lists:
-                if not len(nodes):
-                    continue
-                target = _host_louvain_move(rowptr, col, w, k, comm, tot, size, nodes, resolution, two_m)
-                mv = target != comm[nodes]
-                i, c, d = nodes[mv], comm[nodes][mv], target[mv]
-                np.subtract.at(tot, c, k[i])
-                np.add.at(tot, d, k[i])
-                np.subtract.at(size, c, 1)
-                np.add.at(size, d, 1)
-                comm[i] = d
-                moved += int(mv.sum())
-            history.append(moved)
-            if moved == 0 or jlv.stalled(history):
-                break
-        inside_e = comm[row] == comm[col]
-        inside = np.zeros(n, np.int64)
-        np.add.at(inside, comm, loop)
-        np.add.at(inside, comm[row][inside_e], w[inside_e])
+        history = _host_louvain_sweeps(rowptr, col, w, k, comm, tot, size, resolution, two_m, max_sweeps)
+        inside, _ = _host_louvain_inside(row, col, w, loop, comm)
         q = jlv.modularity_from_tables(inside, tot, two_m, resolution)
         if not q > q_prev + tol:
             break
-        ids, cmap = np.unique(comm, return_inverse=True)
-        cmap = cmap.reshape(-1)
-        nc = len(ids)
-        crow, ccol = cmap[row], cmap[col]
-        new_loop = np.zeros(nc, np.int64)
-        np.add.at(new_loop, cmap, loop)
-        np.add.at(new_loop, crow[inside_e], w[inside_e])
-        keys, inv = np.unique(crow[~inside_e] * nc + ccol[~inside_e], return_inverse=True)
-        new_w = np.zeros(len(keys), np.int64)
-        np.add.at(new_w, inv.reshape(-1), w[~inside_e])
-        new_k = np.zeros(nc, np.int64)
-        np.add.at(new_k, cmap, k)
-        rowptr = np.concatenate([[0], np.cumsum(np.bincount(keys // nc, minlength=nc))]).astype(np.int64)
-        col, w, loop, k = keys % nc, new_w, new_loop, new_k
-        row = np.repeat(np.arange(nc), np.diff(rowptr))
-        levels.append(jlv.level_record(n, nc, history, q, int(k.sum())))
+        rowptr, col, w, loop, k, cmap = _host_louvain_aggregate(row, col, w, loop, k, comm)
+        row = np.repeat(np.arange(len(loop)), np.diff(rowptr))
+        levels.append(jlv.level_record(n, len(loop), history, q, int(k.sum())))
         result = cmap[result]
         q_prev = q
     return dict(comm=result, modularity=q_prev, levels=levels)
@@ -1633,6 +1676,152 @@ def _host_louvain(embeddings, labels, resolution, n_neighbors, max_levels, max_s
         graph = csr_matrix((val, col, rowptr), shape=(len(order), len(order)))
     return jlv.louvain_summary(out['clusters'], out['sizes'], out['modularity'], out['levels'], n_cells, table_mod, table_lab, classes,
                                resolution, n_neighbors, len(col), graph)
+
+
+def _host_leiden_well(x, t, T, gamma, two_m):
+    """wc(x, t) of DESIGN.md §24 on int64 arrays: (double)x >= ((gamma (double)t) (double)(T - t)) / (double)two_m."""
+    return x.astype(np.float64) >= ((gamma * t.astype(np.float64)) * (T - t).astype(np.float64)) / float(two_m)
+
+
+def _host_leiden_targets(rowptr, col, w, k, comm, tot, ref, rtot, rsize, cut, nodes, gamma, two_m):
+    """The targets of `nodes` (int64 ids of one class) from the state as it stands, all rows at once: a
+    node that is no longer alone keeps ref; for the others the entries inside the community are sorted by (node, part), summed per
+    pair in int64 and the admitted pairs ordered by (node, gain descending, part ascending)."""
+    target = ref[nodes].copy()
+    alone = nodes[rsize[ref[nodes]] == 1]
+    if not len(alone):
+        return target
+    lens = rowptr[alone + 1] - rowptr[alone]
+    r = np.repeat(np.arange(len(alone)), lens)
+    e = np.repeat(rowptr[alone] - (np.cumsum(lens) - lens), lens) + np.arange(int(lens.sum()))
+    keep = comm[col[e]] == comm[alone][r]
+    r, s, we = r[keep], ref[col[e[keep]]], w[e[keep]]
+    cut_i = np.zeros(len(alone), np.int64)
+    np.add.at(cut_i, r, we)
+    ki, T = k[alone], tot[comm[alone]]
+    well = _host_leiden_well(cut_i, ki, T, gamma, two_m)
+    if not len(r):
+        return target
+    order = np.lexsort((s, r))
+    r, s, we = r[order], s[order], we[order]
+    starts = np.nonzero(np.concatenate([[True], (r[1:] != r[:-1]) | (s[1:] != s[:-1])]))[0]
+    kis, rg, sg = np.add.reduceat(we, starts), r[starts], s[starts]
+    gain = kis.astype(np.float64) - ((gamma * ki[rg].astype(np.float64)) * rtot[sg].astype(np.float64)) / float(two_m)
+    ok = well[rg] & ~((rsize[sg] == 1) & (sg > alone[rg])) & _host_leiden_well(cut[sg], rtot[sg], T[rg], gamma, two_m) & (gain > 0.0)
+    rg, sg, gain = rg[ok], sg[ok], gain[ok]
+    if len(rg):
+        best = np.lexsort((sg, -gain, rg))
+        rg, sg = rg[best], sg[best]
+        head = np.concatenate([[True], rg[1:] != rg[:-1]])
+        at = np.searchsorted(nodes, alone[rg[head]])             # (`nodes` ascends)
+        target[at] = sg[head]
+    return target
+
+
+def _host_leiden_refine(rowptr, col, w, k, comm, tot, gamma, two_m, trace=None):
+    """DESIGN.md §24 step 3 on the communities comm of a level: (ref, merged, cancelled).  `trace` (a list) receives, per sub-sweep,
+    ref and cut and the two counts so far."""
+    from . import louvain as jlv
+    n = len(k)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    same = comm[row] == comm[col]
+    cls = jlv.node_class(np.arange(n))
+    ref, rtot, rsize = np.arange(n), k.copy(), np.ones(n, np.int64)
+    merged = cancelled = 0
+    for s in range(jlv.CLASSES):
+        nodes = np.nonzero(cls == s)[0]
+        target = ref.copy()
+        leaves = same & (ref[row] != ref[col])
+        cut = np.zeros(n, np.int64)
+        np.add.at(cut, ref[row][leaves], w[leaves])
+        if len(nodes):
+            target[nodes] = _host_leiden_targets(rowptr, col, w, k, comm, tot, ref, rtot, rsize, cut, nodes, gamma, two_m)
+            mv = target[nodes] != ref[nodes]
+            i, d = nodes[mv], target[nodes][mv]
+            stays = target[d] == d
+            cancelled += int((~stays).sum())
+            i, d = i[stays], d[stays]
+            np.subtract.at(rtot, ref[i], k[i])
+            np.add.at(rtot, d, k[i])
+            np.subtract.at(rsize, ref[i], 1)
+            np.add.at(rsize, d, 1)
+            ref[i] = d
+            merged += len(i)
+        if trace is not None:
+            trace.append(dict(ref=ref.copy(), cut=cut, merged=merged, cancelled=cancelled))
+    return ref, merged, cancelled
+
+
+def _host_leiden_levels(rowptr, col, w, loop, resolution=1.0, max_levels=20, max_sweeps=32, trace=None):
+    """DESIGN.md §24 on an integer level graph (rowptr, col, w int64, loop int64) in numpy: dict(comm int64 [n] the returned
+    partition composed down to the level-0 nodes, modularity, levels, stop).  `trace` (a list) receives one list per refined
+    level (`_host_leiden_refine`)."""
+    from . import leiden as jld
+    from . import louvain as jlv
+    rowptr, col = np.asarray(rowptr, np.int64), np.asarray(col, np.int64)
+    w, loop = np.asarray(w, np.int64), np.asarray(loop, np.int64)
+    n = len(loop)
+    row = np.repeat(np.arange(n), np.diff(rowptr))
+    k = loop.copy()
+    np.add.at(k, row, w)
+    two_m = int(k.sum())
+    jlv.check_totals(n, two_m, 'leiden')
+    cells = np.arange(n)
+    comm0, levels = np.arange(n), []
+    while True:
+        n = len(loop)
+        comm, tot, size = comm0.copy(), np.zeros(n, np.int64), np.bincount(comm0, minlength=n).astype(np.int64)
+        np.add.at(tot, comm, k)
+        history = _host_louvain_sweeps(rowptr, col, w, k, comm, tot, size, resolution, two_m, max_sweeps)
+        inside, _ = _host_louvain_inside(row, col, w, loop, comm)
+        q = jlv.modularity_from_tables(inside, tot, two_m, resolution)
+        nc = int((size > 0).sum())
+        if nc == n or len(levels) + 1 >= max_levels:
+            levels.append(jld.level_record(n, nc, history, q, two_m))
+            return dict(comm=comm[cells], modularity=q, levels=levels, stop='singletons' if nc == n else 'max_levels')
+        sub = None
+        if trace is not None:
+            sub = []
+            trace.append(sub)
+        ref, merged, cancelled = _host_leiden_refine(rowptr, col, w, k, comm, tot, resolution, two_m, sub)
+        if merged == 0:
+            levels.append(jld.level_record(n, nc, history, q, two_m, n, 0, cancelled))
+            return dict(comm=cells, modularity=jlv.modularity_from_tables(loop, k, two_m, resolution), levels=levels, stop='stuck')
+        rowptr, col, w, loop, k, cmap = _host_louvain_aggregate(row, col, w, loop, k, ref)
+        row = np.repeat(np.arange(len(loop)), np.diff(rowptr))
+        levels.append(jld.level_record(n, nc, history, q, two_m, len(loop), merged, cancelled))
+        low = np.full(n, len(loop), np.int64)
+        np.minimum.at(low, comm, cmap)
+        comm0 = np.empty(len(loop), np.int64)
+        comm0[cmap] = low[comm]
+        cells = cmap[cells]
+
+
+def _host_leiden_graph(rowptr, col, val, resolution=1.0, max_levels=20, max_sweeps=32, tol=1e-7, trace=None):
+    """`leiden.communities` in numpy on the CSR arrays of any fp32 graph: dict(clusters int32 [N], sizes, modularity, levels,
+    stop).  `tol` is unused."""
+    from . import louvain as jlv
+    n = len(rowptr) - 1
+    out = _host_leiden_levels(rowptr, col, jlv.quantise(val), np.zeros(n, np.int64), resolution, max_levels, max_sweeps, trace)
+    clusters, sizes = jlv.relabel(out['comm'])
+    return dict(clusters=clusters, sizes=sizes, modularity=out['modularity'], levels=out['levels'], stop=out['stop'])
+
+
+def _host_leiden(embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol, return_graph=False):
+    """The dict of `leiden.leiden` in int64 / float64 numpy on `_host_fuzzy_graph`'s graph: the same definition."""
+    from . import leiden as jld
+    from . import louvain as jlv
+    n_cells = [e.shape[0] for e in embeddings]
+    order, dist = _host_sorted_neighbors(embeddings, n_neighbors - 1, 'leiden')
+    W, _, _, _ = _host_smooth_knn(dist, n_neighbors)
+    rowptr, col, val = _host_fuzzy_graph(order, W)
+    out = _host_leiden_graph(rowptr, col, val, resolution, max_levels, max_sweeps, tol)
+    table_mod, table_lab, classes = jlv.host_tables(out['clusters'], n_cells, labels, len(out['sizes']))
+    graph = None
+    if return_graph:
+        from scipy.sparse import csr_matrix
+        graph = csr_matrix((val, col, rowptr), shape=(len(order), len(order)))
+    return jld.leiden_summary(out, n_cells, table_mod, table_lab, classes, resolution, n_neighbors, len(col), graph)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
