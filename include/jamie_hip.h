@@ -63,7 +63,9 @@ typedef struct {
     const float* A; const float* B; float* C;
     const float* bias;          /* [N] or NULL */
     const float* aux0; const float* aux1; const float* aux2; const float* aux3;
-    float* partial;             /* per-block fp32 partial sums (EPI_MSE) or NULL */
+    float* partial;             /* per-tile fp32 partial sums, slot m_tile + tiles_m * n_tile: the MSE term (EPI_MSE), or -- jamie_gemm_bf16,
+                                 * large-tile configurations, EPI_STORE with splitk == 1 -- the sum of squares of the stored tile
+                                 * (the dW launches hand the gradient norm its partial sums); or NULL */
     const int32_t* a_rows;      /* optional row gather for A (NT/NN: A row m -> a_rows[m]) or NULL */
     int M, N, K;
     int lda, ldb, ldc, aux_ld;
@@ -74,10 +76,12 @@ typedef struct {
     float pscale;               /* EPI_MSE: partial[block] = pscale * sum d^2 (e.g. w_rec / (B*d)) */
     int b_tr;                   /* jamie_gemm_bf16 only: B is stored [K, N] row-major (N contiguous, ldb >= N) -- the dX
                                  * product dy W reads the weights W [out, in] as they are (model.py Linear backward), no
-                                 * transposed copy; large-tile configurations with 128 columns (23, 24, 25) */
+                                 * transposed copy; any large-tile configuration whose tile has 128 columns (23, 24, 25, 29 - 34; the
+                                 * engine's dX launches run on 29) */
     int a_tr;                   /* jamie_gemm_bf16 only, with b_tr: A is stored [K, M] row-major (lda >= M) -- dW = dy^T a
                                  * reads dy [B, out] and a [B, in] as the layers produced them, no transposed activation
-                                 * copies; 128 x 128 large-tile configurations (24, 25) */
+                                 * copies; the 128 x 128 large-tile configurations (24, 25, 29, 30, 32, 33, 34; the engine's dW
+                                 * launches run on 29) */
     int store_nt;               /* non-temporal output stores (large-tile jamie_gemm_bf16 configurations, jamie_gemm_f32): for
                                  * outputs that are next read much later, e.g. weight gradients (read by the optimiser after the
                                  * whole backward pass) */
