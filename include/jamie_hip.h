@@ -611,6 +611,34 @@ int jamie_lisi(const int32_t* idx, const float* dist, long long N, int K, const 
                double* lisi, int32_t* tries, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Layout quality on the device (jamie_amd/coranking.py): where the entries of a neighbour list -- made in another space of the
+ * same cells -- rank in the space X, fp32 [N, L] row-major: what trustworthiness, continuity and the co-ranking curve Q_NX are
+ * sums of.  q and the order (q ascending, then the lower index) as in "Neighbourhoods on the device": an entry that
+ * jamie_self_knn on X puts at list position p has rank p.  Nothing of size N x N is stored.  Integer counts only: bit-identical
+ * from run to run and for every seg_rows.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `ws` for jamie_list_ranks(N, K, seg_rows): one threshold q per list entry.  0 for N < 2, K outside 1 .. 64 or a
+ * seg_rows that jamie_list_ranks refuses */
+long long jamie_list_ranks_workspace(long long N, int K, long long seg_rows);
+/* rank[i, t] = #{ l != i : (q(i, l), l) < (q(i, j), j) }, j = idx[i, t]: idx int32 [N, K] in any order within a row, rank int32
+ * [N, K], 0-based (the nearest other row has rank 0).  Row i is excluded BY INDEX; a copy of it elsewhere counts, at q = 0.  An
+ * entry with j == i or j outside [0, N) gets -1 and counts nothing; a value that repeats within a row gets the same rank each
+ * time.  The threshold q(i, j) of every entry is formed first, by the chain of the pair tile, into ws: both sides of every
+ * comparison carry the same rounding, and integer-valued data is exact.  A NaN q (inf - inf) is read as +inf on both sides.
+ * 1 <= K <= 64, 2 <= N < 2^31, L >= 1.  seg_rows: rows of X per segment of the walked side, 0 (the library's choice) or a
+ * positive multiple of 128; the segments' counts are integers added into rank and the result does not depend on seg_rows.
+ * Anything else, more than 65535 segments or a ws below jamie_list_ranks_workspace(N, K, seg_rows) returns an error before a
+ * launch and leaves rank as it was */
+int jamie_list_ranks(const float* X, long long N, int L, const int32_t* idx, int K, int32_t* rank, long long seg_rows, void* ws,
+                     long long ws_bytes, void* stream);
+/* The integer sums the curves are made of, from rank int32 [N, K] whose column p belongs to list position p (nearest first):
+ * penalty[k - 1] = sum_i sum_{p < k} max(0, rank[i, p] + 1 - k) and overlap[k - 1] = sum_i #{ p < k : 0 <= rank[i, p] < k } for
+ * k = 1 .. K (int64 [K] each), cell_penalty[i] = sum_{p < K} max(0, rank[i, p] + 1 - K) (int64 [N]).  Negative ranks count
+ * nothing.  1 <= K <= 64, N >= 1 */
+int jamie_coranking_sums(const int32_t* rank, long long N, int K, long long* penalty, long long* overlap, long long* cell_penalty,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clustering on the device (jamie_amd/clustering.py): Lloyd's k-means of one fp32 [N, L] row-major matrix with k <= 1024 centres,
  * the two kernels of k-means++ seeding, and the contingency table of two code arrays.  q(i, j) = sum_c (X[i, c] - C[j, c])^2 as in
  * "Alignment metrics on the device": the same chain in ascending c, exact on integer-valued data.  label[i] = argmin_j by (q, then

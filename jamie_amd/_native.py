@@ -228,6 +228,10 @@ EXPORTS = {
                                  C.c_longlong, C.c_void_p]),
     'jamie_lisi': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                              C.c_void_p, C.c_void_p]),
+    'jamie_list_ranks_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_longlong]),
+    'jamie_list_ranks': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                   C.c_longlong, C.c_void_p]),
+    'jamie_coranking_sums': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'jamie_kmeans_workspace': (C.c_longlong, [C.c_longlong, C.c_int, C.c_int, C.c_longlong]),
     'jamie_kmeans_step': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
@@ -868,6 +872,22 @@ def self_knn(X, K, idx, dist, ws, seg_rows=0):
 def lisi(idx, dist, codes, perplexity, out, tries=None):
     _call('jamie_lisi', ptr(idx), ptr(dist), idx.shape[0], idx.shape[1], ptr(codes), codes.shape[0], float(perplexity), ptr(out),
           ptr(tries), _stream())
+
+
+# ---- layout quality (jamie_amd/coranking.py; include/jamie_hip.h "Layout quality on the device") ----
+def list_ranks_workspace(N, K, seg_rows=0):
+    """Bytes of workspace for list_ranks on N rows; 0 for arguments jamie_list_ranks refuses.  Host arithmetic."""
+    return int(load().jamie_list_ranks_workspace(int(N), int(K), int(seg_rows)))
+
+
+def list_ranks(X, idx, rank, ws, seg_rows=0):
+    """rank[i, t] (int32 [N, K]) = the rows other than i that lie before row idx[i, t] in the order (q(i, .), index) of X."""
+    _call('jamie_list_ranks', ptr(X), X.shape[0], X.shape[1], ptr(idx), idx.shape[1], ptr(rank), int(seg_rows), ptr(ws),
+          ws.numel() * ws.element_size(), _stream())
+
+
+def coranking_sums(rank, penalty, overlap, cell_penalty):
+    _call('jamie_coranking_sums', ptr(rank), rank.shape[0], rank.shape[1], ptr(penalty), ptr(overlap), ptr(cell_penalty), _stream())
 
 
 # ---- clustering (jamie_amd/clustering.py; include/jamie_hip.h "Clustering on the device") ----

@@ -1052,6 +1052,27 @@ class JAMIE:
             return jnb.knn_graph(integrated_data, k=k, mode=mode, device=self.device)
         return _host_neighbors([_host_array(e) for e in integrated_data], k, mode)
 
+    def test_layout(self, integrated_data, layout, n_neighbors=15, return_ranks=False):
+        """How well `layout` keeps the neighbourhoods of `integrated_data`: any two representations of the same cells, one array
+        per modality each, pooled.  Two uses: an embedding against its 2-D picture (`tsne`, `umap`, `spectral`), and `jm.dataset`
+        against the integrated embedding (how much of each modality's measured structure the integration keeps).  Returns
+        `trustworthiness` and `continuity` at K = n_neighbors (sklearn's definition; 1 <= K < cells / 2, K <= 64), their
+        `*_curve` over k = 1 .. K, the co-ranking curve `qnx`, `lcmc` and its argmax `k_best`, the per-cell terms
+        `cell_trustworthiness` / `cell_continuity` (one array per modality, to colour the plot with), `n_neighbors`, `n_cells`
+        and, with `return_ranks`, the rank arrays and the lists.  metrics='host': float64 numpy on N x N distances, for a few
+        thousand cells; metrics='device': jamie_amd/coranking.py `neighborhood_preservation`."""
+        from . import coranking as jcr
+        n_cells = jcr.check_spaces(integrated_data, layout, 'test_layout')
+        k = jcr.check_neighbors(n_neighbors, int(sum(n_cells)), 'test_layout')
+        if self.metrics == 'device':
+            out = jcr.neighborhood_preservation(integrated_data, layout, n_neighbors=k, device=self.device,
+                                                return_ranks=return_ranks)
+        else:
+            out = _host_layout([_host_array(e) for e in integrated_data], [_host_array(e) for e in layout], k, return_ranks)
+        print(f"trustworthiness: {out['trustworthiness']}")
+        print(f"continuity: {out['continuity']}")
+        return out
+
     def test_clustering(self, integrated_data, datatype=None, n_clusters=None, n_init=4, max_iter=300, tol=1e-4, seed=0, init=None):
         """k-means of the pooled embeddings and how well the clusters recover the labels: `clusters` (int32 ids,
         one array per embedding), `centers` [k, L], `inertia`, `n_iter`, `converged`, `sizes` [k], `n_empty`, `run` (the winning
@@ -1315,6 +1336,39 @@ def _host_neighbors(embeddings, k, mode):
     from . import neighbors as jnb
     order, dist = _host_sorted_neighbors(embeddings, k, 'neighbors')
     return jnb.graph_from_lists(order, dist, mode)
+
+
+def _host_full_ranks(embeddings, what):
+    """pos int32 [N, N] of the pooled cells: pos[i, j] = the 0-based rank of cell j among the other cells by (float64
+    direct-difference distance to cell i, then lower index); N - 1 on the diagonal."""
+    from scipy.spatial.distance import cdist
+    for e in embeddings:
+        if e.ndim != 2 or e.shape[1] != embeddings[0].shape[1] or e.shape[1] < 1:
+            raise ValueError(f'{what}: the arrays of one space must be [cells, features] with the same features')
+    X = np.concatenate([np.asarray(e, dtype=np.float64) for e in embeddings], axis=0)
+    if not np.isfinite(X).all():
+        raise ValueError(f'{what}: input contains NaN or infinity')
+    d = cdist(X, X)
+    np.fill_diagonal(d, np.inf)
+    order = np.argsort(d, axis=1, kind='stable')
+    pos = np.empty(order.shape, np.int32)
+    np.put_along_axis(pos, order, np.arange(len(X), dtype=np.int32)[None, :], axis=1)
+    return pos, order
+
+
+def _host_layout(high, low, k, return_ranks=False):
+    """The dict of `coranking.neighborhood_preservation` in float64 numpy, on the N x N distance matrices of both spaces."""
+    from . import coranking as jcr
+    n_cells = jcr.check_spaces(high, low, 'test_layout')
+    pos_high, order_high = _host_full_ranks(high, 'test_layout')
+    pos_low, order_low = _host_full_ranks(low, 'test_layout')
+    idx_high, idx_low = order_high[:, :k], order_low[:, :k]
+    rank_high = np.take_along_axis(pos_high, idx_low, axis=1)
+    rank_low = np.take_along_axis(pos_low, idx_high, axis=1)
+    out = jcr.preservation_summary(n_cells, k, jcr.host_rank_sums(rank_high), jcr.host_rank_sums(rank_low))
+    if return_ranks:
+        out.update(rank_high=rank_high, rank_low=rank_low, idx_high=idx_high.astype(np.int32), idx_low=idx_low.astype(np.int32))
+    return out
 
 
 def _host_affinities(dist, perplexity):
