@@ -942,6 +942,37 @@ int jamie_leiden_apply(const int32_t* nodes, long long count, const int32_t* tar
                        long long* rtot, int32_t* rsize, long long* counts, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Graph structure on the device (jamie_amd/graph.py): the connected components of a CSR graph of n < 2^31 nodes
+ * (rowptr[n + 1] int64, col[nnz] int32; values are not read) by synchronous min-label hooking, and the kBET statistic of every
+ * cell from its neighbour lists.  The state of the components is root[n] (int32: the smallest node id known for the node's tree,
+ * root[root[i]] == root[i]) and the work array parent[n].  A round copies root to parent, hooks (jamie_graph_hook), then
+ * compresses parent by jump passes (jamie_graph_jump, ping-pong) until a pass changes nothing: that is the next root.  The run
+ * ends with the first round whose hook finds nothing; root[i] is then the smallest node id of i's component.  An entry (i, j)
+ * counts when 0 <= j < n, j != i and (group == NULL or group[i] == group[j]); it links both ways whether or not its mirror is
+ * stored (weak connectivity).  Duplicate entries, self loops and empty rows are legal; row extents are clamped to [0, nnz].
+ * Every read of a hook comes from its input and the only atomics are integer minima, so the array after every launch is a
+ * function of the launch's input: the same bits from run to run, equal to a restatement in any order.
+ * ------------------------------------------------------------------------------------------------ */
+/* for every entry (i, j) that counts, with a = root[i], b = root[j], a != b: parent[max(a, b)] = min(parent[max(a, b)], min(a, b))
+ * (integer atomics) and *changed = 1 (int32 on the device, never cleared here).  `parent` holds a copy of `root` on entry and is
+ * another array; `root` is only read.  A root outside [0, n) hooks nothing */
+int jamie_graph_hook(const long long* rowptr, const int32_t* col, long long nnz, long long n, const int32_t* group,
+                     const int32_t* root, int32_t* parent, int32_t* changed, void* stream);
+/* out[i] = in[in[i]] for the n nodes (in[i] itself where it is outside [0, n)); *changed = 1 when some out[i] != in[i] (never
+ * cleared here).  `out` is another array */
+int jamie_graph_jump(const int32_t* in, int32_t* out, long long n, int32_t* changed, void* stream);
+/* kBET's statistic of cell i from its K listed neighbours idx[N, K] (int32) under the categories codes[N] (int32) and the
+ * expected shares expected[n_e, B] (fp64), of which the cell uses row erow[i] (row 0 when erow is NULL):
+ *     o_b = #{t < K : 0 <= idx[i, t] < N and codes[idx[i, t]] == b}      (an entry or a code outside its range counts nowhere)
+ *     k_i = sum_b o_b,  e_b = (double)k_i * expected[erow[i], b]
+ *     stat[i] = the sum in ascending b, over the b with expected > 0, of ((o_b - e_b) * (o_b - e_b)) / e_b
+ * (fp64, this order, no contraction) and df[i] = #{b : expected > 0} - 1.  When k_i = 0, df[i] < 1, a category with o_b > 0 has
+ * expected 0, or erow[i] is outside [0, n_e): stat[i] = NaN and df[i] = 0 (the cell is not tested).  counts[N, B] (int32, may be
+ * NULL) receives o.  1 <= K <= 128, 1 <= B <= 64 */
+int jamie_kbet_stat(const int32_t* idx, long long N, int K, const int32_t* codes, int B, const double* expected, int n_e,
+                    const int32_t* erow, double* stat, int32_t* df, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Sparse cell matrices (jamie_amd/sparse_input.py): `preclass(sample, axis=0)` of the reference (utilities.py:654-678; built at
  * jamie.py:462-465, applied at jamie.py:508 to the fitting sample and at jamie.py:806-837 to new cells in modal_predict /
  * transform / transform_one) for a scipy CSR matrix of N cells x d features, without a dense copy of the input on the host or the

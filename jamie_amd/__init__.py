@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ('TrainEngine',):
         from .engine import TrainEngine
         return TrainEngine
+    if name in ('components',):
+        from .graph import components
+        return components
     raise AttributeError(name)

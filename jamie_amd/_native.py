@@ -291,6 +291,11 @@ EXPORTS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     'jamie_leiden_apply': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),
+    'jamie_graph_hook': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    'jamie_graph_jump': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'jamie_kbet_stat': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     'jamie_sparse_workspace': (C.c_longlong, [C.c_void_p, C.c_int, C.c_int]),
     'jamie_csc_col_stats': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
@@ -1071,6 +1076,23 @@ def leiden_refine(rowptr, col, w, k, comm, tot, ref, rtot, rsize, cut, gamma, tw
 def leiden_apply(nodes, target, k, ref, rtot, rsize, counts):
     _call('jamie_leiden_apply', ptr(nodes), int(nodes.numel()), ptr(target), ptr(k), ptr(ref), ptr(rtot), ptr(rsize), ptr(counts),
           k.shape[0], _stream())
+
+
+# ---- graph structure (jamie_amd/graph.py; include/jamie_hip.h "Graph structure on the device") ----
+def graph_hook(rowptr, col, group, root, parent, changed):
+    """`parent` holds a copy of `root`; `group` int32 [n] or None."""
+    _call('jamie_graph_hook', ptr(rowptr), ptr(col), int(col.numel()), root.shape[0], ptr(group), ptr(root), ptr(parent), ptr(changed),
+          _stream())
+
+
+def graph_jump(src, out, changed):
+    _call('jamie_graph_jump', ptr(src), ptr(out), src.shape[0], ptr(changed), _stream())
+
+
+def kbet_stat(idx, codes, expected, erow, stat, df, counts=None):
+    """expected float64 [n_e, B]; erow int32 [N] or None; counts int32 [N, B] or None."""
+    _call('jamie_kbet_stat', ptr(idx), idx.shape[0], idx.shape[1], ptr(codes), expected.shape[1], ptr(expected), expected.shape[0],
+          ptr(erow), ptr(stat), ptr(df), ptr(counts), _stream())
 
 
 # ---- sparse cell matrices (jamie_amd/sparse_input.py; include/jamie_hip.h "Sparse cell matrices") ----

@@ -1195,6 +1195,30 @@ class JAMIE:
               f"{out['modularity']:.6f}, ARI {out['ari']}")
         return out
 
+    def test_graph(self, integrated_data, datatype=None, n_neighbors=15, alpha=0.05, expected='global', return_graph=False):
+        """Connected components, graph connectivity and kBET of the pooled embeddings on the fuzzy graph of `umap` (DESIGN.md
+        §26; scIB's `graph_connectivity` and `kBET`).  `components` (int32 ids by descending size, one array per embedding),
+        `n_components`, `component_sizes`, `largest_share`, `modality_contingency` [components, M], `label_contingency`, `rounds`
+        and `jumps` of the min-label rounds; with labels `graph_connectivity` (the mean over labels of `label_connectivity` [T]:
+        the share of a label's cells in the largest component of the graph cut down to that label), `label_components` [T] and the
+        `labels` in `np.unique` order (each None without labels); with two or more embeddings `kbet_rejection` (the share of
+        tested cells whose n_neighbors - 1 neighbours hold the modalities in other than the expected shares, chi-square at level
+        `alpha`), `kbet_acceptance`, `kbet_pvalues` and `kbet_stat` per embedding (NaN where a cell is not tested), `kbet_tested`
+        and `label_kbet_rejection` [T] (each None for a single embedding); `n_neighbors`, `n_edges`, `alpha`, `expected` and `graph`
+        (scipy CSR with `return_graph`).  expected='global': the modality shares of the pooled cells; 'label': the shares among
+        the cells of the cell's own label (build-defined).  No subsampling and no permutation null.  metrics='host': scipy's
+        `connected_components` and float64 numpy on N x N distances, for a few thousand cells; metrics='device':
+        jamie_amd/graph.py `graph_metrics`."""
+        from . import graph as jgr
+        checked = jgr.check_graph_metrics(integrated_data, datatype, n_neighbors, alpha, expected, 'test_graph')
+        if self.metrics == 'device':
+            out = jgr.graph_metrics_checked(integrated_data, datatype, *checked, return_graph, self.device)
+        else:
+            out = _host_test_graph([_host_array(e) for e in integrated_data], datatype, *checked, return_graph)
+        print(f"test_graph: {out['n_components']} components (largest {out['largest_share']:.4f}), graph connectivity "
+              f"{out['graph_connectivity']}, kBET rejection {out['kbet_rejection']}")
+        return out
+
     def test_imputation(self, imputed, measured, threshold=0.0):
         """Per-feature imputation figures (reference evaluation.py): {'correlation', 'mse', 'auroc'}, float64 [features] each,
         between imputed values (`modal_predict`) and the measured ones.  AUROC scores the imputed value against `measured >
@@ -1876,6 +1900,73 @@ def _host_leiden(embeddings, labels, resolution, n_neighbors, max_levels, max_sw
         from scipy.sparse import csr_matrix
         graph = csr_matrix((val, col, rowptr), shape=(len(order), len(order)))
     return jld.leiden_summary(out, n_cells, table_mod, table_lab, classes, resolution, n_neighbors, len(col), graph)
+
+
+def _host_components(rowptr, col, n, cells=None):
+    """The smallest member of every node's component (int32 [n]) by scipy's `connected_components` (weak); `cells`: the nodes of
+    the induced subgraph to look at (their entries in the result; the other entries are -1)."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import connected_components
+    A = csr_matrix((np.ones(len(col), np.int8), np.asarray(col), np.asarray(rowptr)), shape=(n, n))
+    cells = np.arange(n) if cells is None else np.asarray(cells)
+    _, lab = connected_components(A[cells][:, cells], directed=True, connection='weak')
+    first = np.full(lab.max() + 1, n, dtype=np.int64)
+    np.minimum.at(first, lab, cells)
+    out = np.full(n, -1, dtype=np.int32)
+    out[cells] = first[lab]
+    return out
+
+
+def _host_kbet(order, codes, shares, erow):
+    """`jamie_kbet_stat` in float64 numpy: (stat [N], df [N], counts [N, B]) from `np.bincount` counts, the sum taken category
+    after category in ascending order."""
+    N, B = len(order), shares.shape[1]
+    counts = np.stack([np.bincount(codes[order[i]], minlength=B) for i in range(N)]).astype(np.int64)
+    f = shares[np.zeros(N, np.int64) if erow is None else erow]
+    k = counts.sum(axis=1).astype(np.float64)
+    stat, cats = np.zeros(N), np.zeros(N, np.int64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for b in range(B):
+            e = k * f[:, b]
+            d = counts[:, b] - e
+            have = f[:, b] > 0
+            stat = np.where(have, stat + (d * d) / e, stat)
+            cats += have
+    tested = (k > 0) & (cats >= 2) & ~((counts > 0) & ~(f > 0)).any(axis=1)
+    return np.where(tested, stat, np.nan), np.where(tested, cats - 1, 0).astype(np.int32), counts
+
+
+def _host_test_graph(embeddings, labels, n_neighbors, alpha, expected, return_graph=False):
+    """The dict of `graph.graph_metrics` on `_host_fuzzy_graph`'s graph: the components by scipy (per label on the induced
+    subgraph), the round counts by the numpy rounds, kBET in float64 numpy: the same definition."""
+    from . import graph as jgr
+    from . import neighbors as jnb
+    n_cells = [e.shape[0] for e in embeddings]
+    mod, lcode, classes = jnb.pooled_codes(n_cells, labels, 'test_graph')
+    order, dist = _host_sorted_neighbors(embeddings, n_neighbors - 1, 'test_graph')
+    W, _, _, _ = _host_smooth_knn(dist, n_neighbors)
+    rowptr, col, val = _host_fuzzy_graph(order, W)
+    N = len(order)
+    label = _host_components(rowptr, col, N)
+    _, rounds, jumps = jgr.host_rounds(rowptr, col, N)
+    share = count = None
+    if lcode is not None:
+        glabel = np.full(N, -1, dtype=np.int32)
+        for t in range(len(classes)):
+            cells = np.nonzero(lcode == t)[0]
+            glabel[cells] = _host_components(rowptr, col, N, cells)[cells]
+        share, count = jgr.label_connectivity(glabel, lcode, len(classes))
+    kbet = None
+    if len(embeddings) > 1:
+        shares, erow = jgr.expected_rows(mod, len(embeddings), lcode, None if classes is None else len(classes), expected)
+        stat, df, _ = _host_kbet(order, mod, shares, erow)
+        kbet = dict(stat=stat, df=df)
+    graph = None
+    if return_graph:
+        from scipy.sparse import csr_matrix
+        graph = csr_matrix((val, col, rowptr), shape=(N, N))
+    return jgr.graph_summary(label, rounds, jumps, n_cells, lcode, classes, share, count, kbet, n_neighbors, len(col), alpha, expected,
+                             graph)
 
 
 def _host_kmeans(X, k, n_init, max_iter, tol, seed, init):
