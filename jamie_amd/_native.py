@@ -1040,12 +1040,17 @@ def louvain_workspace(lens):
     return int(load().jamie_louvain_workspace(lens.ctypes.data, len(lens)))
 
 
-def louvain_move(rowptr, col, w, k, comm, tot, size, gamma, two_m, nodes, counts, slot_off, ws, target, flag):
-    """`nodes`: the list from its first short row on; counts = (short, long, global); slot_off int64 [global + 1] or None."""
+def _node_list_args(nodes, counts, slot_off, ws, target, flag):
+    """The arguments louvain_move and leiden_refine end in.  `nodes`: the list from its first short row on; counts = (short, long,
+    global); slot_off int64 [global + 1] or None."""
     n_slots = int(slot_off[-1].item()) if counts[2] else 0
+    return (ptr(nodes), int(counts[0]), int(counts[1]), int(counts[2]), ptr(slot_off), n_slots, ptr(ws), ws.numel() * ws.element_size(),
+            ptr(target), ptr(flag), _stream())
+
+
+def louvain_move(rowptr, col, w, k, comm, tot, size, gamma, two_m, nodes, counts, slot_off, ws, target, flag):
     _call('jamie_louvain_move', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), k.shape[0], ptr(k), ptr(comm), ptr(tot), ptr(size),
-          float(gamma), int(two_m), ptr(nodes), int(counts[0]), int(counts[1]), int(counts[2]), ptr(slot_off), n_slots, ptr(ws),
-          ws.numel() * ws.element_size(), ptr(target), ptr(flag), _stream())
+          float(gamma), int(two_m), *_node_list_args(nodes, counts, slot_off, ws, target, flag))
 
 
 def louvain_apply(nodes, target, k, comm, tot, size, moved):
@@ -1066,11 +1071,8 @@ def leiden_cut(rowptr, col, w, comm, ref, cut):
 
 
 def leiden_refine(rowptr, col, w, k, comm, tot, ref, rtot, rsize, cut, gamma, two_m, nodes, counts, slot_off, ws, target, flag):
-    """`nodes`: the list from its first short row on; counts = (short, long, global); slot_off int64 [global + 1] or None."""
-    n_slots = int(slot_off[-1].item()) if counts[2] else 0
     _call('jamie_leiden_refine', ptr(rowptr), ptr(col), ptr(w), int(col.numel()), k.shape[0], ptr(k), ptr(comm), ptr(tot), ptr(ref),
-          ptr(rtot), ptr(rsize), ptr(cut), float(gamma), int(two_m), ptr(nodes), int(counts[0]), int(counts[1]), int(counts[2]),
-          ptr(slot_off), n_slots, ptr(ws), ws.numel() * ws.element_size(), ptr(target), ptr(flag), _stream())
+          ptr(rtot), ptr(rsize), ptr(cut), float(gamma), int(two_m), *_node_list_args(nodes, counts, slot_off, ws, target, flag))
 
 
 def leiden_apply(nodes, target, k, ref, rtot, rsize, counts):

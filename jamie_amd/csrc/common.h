@@ -21,11 +21,13 @@ inline int jamie_fail(int code, const char* fmt, const char* a = "", long long b
     return code;
 }
 
-#define JAMIE_ARG(cond, msg)                                                                        \
+// `who`: the entry point the refusal names (a helper that checks on behalf of one passes its caller's name)
+#define JAMIE_ARG_AS(who, cond, msg)                                                                \
     do {                                                                                            \
-        if (!(cond)) return jamie_fail(-1, "%s: argument check failed: " msg " [%lld %lld]", __func__, \
+        if (!(cond)) return jamie_fail(-1, "%s: argument check failed: " msg " [%lld %lld]", who,   \
                                        0, 0);                                                       \
     } while (0)
+#define JAMIE_ARG(cond, msg) JAMIE_ARG_AS(__func__, cond, msg)
 
 inline int jamie_launch_status(const char* who) {
     hipError_t e = hipGetLastError();

@@ -5,12 +5,11 @@ and aggregation by the parts, on the integer level graphs of jamie_amd/louvain.p
     start(G)                                           every node alone: ref, rtot, rsize (and the cut table, the targets, the counts)
     cut_table(G, comm, R), refine, apply               one class's sub-sweep: the cut of every part, the targets, their application
     refine_level(G, state, R, gamma)                   the 8 sub-sweeps of a level's refinement; (merged, cancelled)
-    move_phase(G, comm0, gamma, max_sweeps)            Louvain's sweeps from the partition comm0; (state, the moved history)
     next_partition(comm, cmap, nc)                     the start partition of the next level: the lowest part of every community
     communities(graph), leiden(embeddings, labels)     the whole run on a `FuzzyGraph`; JAMIE.leiden on the device
 
 The kernels are in csrc/leiden.hip (include/jamie_hip.h, "Leiden communities on the device").  The graph, the level graph, a sweep,
-the aggregation, the tables of Q and the summary are louvain.py's.  The definition (shared with the int64 / float64 host route of
+the move phase (`run_level` from a partition), the aggregation, the tables of Q, the summary and the pooled front end are louvain.py's.  The definition (shared with the int64 / float64 host route of
 jamie.py) is DESIGN.md §24: every sum of weights is an int64 sum, so the device route equals a numpy restatement element for
 element and run for run, and every returned community is connected unless the run stopped at max_levels.
 """
@@ -18,8 +17,6 @@ import torch
 
 from . import _native as nv
 from . import louvain as jlv
-from .clustering import contingency
-from .neighbors import _n_rows, _pool, pooled_codes
 
 STOPS = ('singletons', 'stuck', 'max_levels')
 
@@ -68,23 +65,20 @@ def refine(G, state, R, cls, gamma=1.0):
     """The targets of the nodes of class `cls` from the state as it stands, into R.target (the other classes' entries are left
     alone); the (short, long, global) row counts the launch took."""
     nv.require_gpu()
-    p = G.plan()
-    counts = [int(c) for c in p['counts'][cls]]
+    nodes, counts, slot_off, ws = G.of_class(cls)
     if sum(counts):
-        first = int(p['starts'][3 * cls])
         nv.leiden_refine(G.rowptr, G.col, G.w, G.k, state.comm, state.tot, R.ref, R.rtot, R.rsize, R.cut, float(gamma), G.two_m,
-                         p['nodes'][first:], counts, p['slot_off'][cls], p['ws'], R.target, R.flag)
-    return tuple(counts)
+                         nodes, counts, slot_off, ws, R.target, R.flag)
+    return counts
 
 
 def apply(G, R, cls):
     """Applies R.target to the nodes of class `cls`: ref, rtot, rsize by integer atomics; R.counts grows by the merged and the
     cancelled moves."""
     nv.require_gpu()
-    p = G.plan()
-    first, count = int(p['starts'][3 * cls]), int(p['counts'][cls].sum())
-    if count:
-        nv.leiden_apply(p['nodes'][first:first + count], R.target, G.k, R.ref, R.rtot, R.rsize, R.counts)
+    nodes = G.of_class(cls)[0]
+    if nodes.numel():
+        nv.leiden_apply(nodes, R.target, G.k, R.ref, R.rtot, R.rsize, R.counts)
 
 
 def refine_level(G, state, R, gamma=1.0, trace=None):
@@ -106,17 +100,6 @@ def refine_level(G, state, R, gamma=1.0, trace=None):
     return merged, cancelled
 
 
-def move_phase(G, comm0, gamma, max_sweeps):
-    """Louvain's sweeps from the partition comm0 (None: singletons): (state, the moved history)."""
-    state = jlv.singletons(G) if comm0 is None else jlv.state_of(G, comm0)
-    history = []
-    for _ in range(max_sweeps):
-        history.append(jlv.sweep(G, state, gamma))
-        if history[-1] == 0 or jlv.stalled(history):
-            break
-    return state, history
-
-
 def next_partition(comm, cmap, nc):
     """comm0 int32 [nc] of the next level: every part r starts in the lowest coarse id among the parts of its community.  Integer
     `scatter_reduce` (amin) and a scatter of equal values."""
@@ -135,7 +118,7 @@ def communities_of_level_graph(G, resolution=1.0, max_levels=20, max_sweeps=32, 
     cells = torch.arange(G.n, dtype=torch.int64, device=G.col.device)
     comm0, levels = None, []
     while True:
-        state, history = move_phase(G, comm0, resolution, max_sweeps)
+        state, history = jlv.run_level(G, resolution, max_sweeps, comm0)      # the move phase: DESIGN.md §23 steps 2-3
         inside = jlv.internal_weights(G, state.comm)
         q = jlv.modularity_from_tables(inside.cpu().numpy(), state.tot.cpu().numpy(), two_m, resolution)
         nc = int((state.size > 0).sum().item())
@@ -170,7 +153,7 @@ def communities(graph, resolution=1.0, max_levels=20, max_sweeps=32, tol=1e-7, t
 
 def leiden_summary(out, *rest):
     """`louvain_summary`'s dict and `stop`."""
-    res = jlv.louvain_summary(out['clusters'], out['sizes'], out['modularity'], out['levels'], *rest)
+    res = jlv.run_summary(out, *rest)
     res['stop'] = out['stop']
     return res
 
@@ -191,14 +174,5 @@ def leiden(embeddings, labels=None, resolution=1.0, n_neighbors=15, max_levels=2
 
 def leiden_checked(embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol, return_graph=False, device='cuda'):
     """`leiden` behind its argument checks: the arguments are what `check_louvain` returned."""
-    from .spectral import build_graph
-    n_cells = [_n_rows(e) for e in embeddings]
-    mod, lcode, classes = pooled_codes(n_cells, labels, 'leiden')
-    xs, x = _pool(embeddings, device, 'leiden')
-    G = build_graph(x, n_neighbors, device)
-    out = communities(G, resolution, max_levels, max_sweeps, tol)
-    k = len(out['sizes'])
-    table_mod = contingency(out['clusters'], mod, k, len(xs), device=x.device)
-    table_lab = None if lcode is None else contingency(out['clusters'], lcode, k, len(classes), device=x.device)
-    graph = G.to_scipy() if return_graph else None
-    return leiden_summary(out, n_cells, table_mod, table_lab, classes, resolution, n_neighbors, G.col.numel(), graph)
+    return jlv.pooled_run('leiden', communities, leiden_summary, embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps,
+                          tol, return_graph, device)

@@ -27,7 +27,7 @@ CLASSES = 8                    # sub-sweeps of a sweep
 CLASS_MULT = 2654435761
 CLASS_SHIFT = 7
 PATIENCE = 3
-# the bins of jamie_louvain_move (csrc/louvain.hip LV_SHORT_MAX, LV_LONG_MAX): a row of at most SHORT_MAX entries is a wave's,
+# the bins of jamie_louvain_move (csrc/community_rows.h CR_SHORT_MAX, CR_LONG_MAX): a row of at most SHORT_MAX entries is a wave's,
 # one of at most LONG_MAX a workgroup's with its table in LDS, a longer one a workgroup's with its table in the workspace
 SHORT_MAX = 64
 LONG_MAX = 2048
@@ -135,7 +135,7 @@ def host_tables(clusters, n_cells, labels, k):
 
 
 def table_slots(length):
-    """Slots of the workspace table of a row of `length` entries: the power of two from 2 length + 2 up (csrc/louvain.hip)."""
+    """Slots of the workspace table of a row of `length` entries: the power of two from 2 length + 2 up (csrc/community_rows.h)."""
     s = 2
     while s < 2 * int(length) + 2:
         s *= 2
@@ -205,6 +205,14 @@ class LevelGraph:
             self._plan = dict(nodes=nodes, counts=counts, starts=starts, slot_off=slot_off, ws=ws)
         return self._plan
 
+    def of_class(self, cls):
+        """What a launch over the nodes of class `cls` takes from the plan: (its node list in bin order, its (short, long, global)
+        counts, the slot offsets of its workspace tables or None, the workspace)."""
+        p = self.plan()
+        counts = tuple(int(c) for c in p['counts'][cls])
+        first = int(p['starts'][3 * cls])
+        return p['nodes'][first:first + sum(counts)], counts, p['slot_off'][cls], p['ws']
+
 
 class State:
     """comm int32 [n], tot int64 [n], size int32 [n] of a level on the device, and the targets of the last `move`."""
@@ -247,22 +255,19 @@ def move(G, state, cls, gamma=1.0):
     """The targets of the nodes of class `cls` from the state as it stands, into state.target (the other classes' entries are left
     alone); the (short, long, global) row counts the launch took."""
     nv.require_gpu()
-    p = G.plan()
-    counts = [int(c) for c in p['counts'][cls]]
+    nodes, counts, slot_off, ws = G.of_class(cls)
     if sum(counts):
-        first = int(p['starts'][3 * cls])
-        nv.louvain_move(G.rowptr, G.col, G.w, G.k, state.comm, state.tot, state.size, float(gamma), G.two_m, p['nodes'][first:],
-                        counts, p['slot_off'][cls], p['ws'], state.target, state.flag)
-    return tuple(counts)
+        nv.louvain_move(G.rowptr, G.col, G.w, G.k, state.comm, state.tot, state.size, float(gamma), G.two_m, nodes, counts, slot_off,
+                        ws, state.target, state.flag)
+    return counts
 
 
 def apply(G, state, cls):
     """Applies state.target to the nodes of class `cls`: comm, tot, size by integer atomics; state.moved grows by the moves."""
     nv.require_gpu()
-    p = G.plan()
-    first, count = int(p['starts'][3 * cls]), int(p['counts'][cls].sum())
-    if count:
-        nv.louvain_apply(p['nodes'][first:first + count], state.target, G.k, state.comm, state.tot, state.size, state.moved)
+    nodes = G.of_class(cls)[0]
+    if nodes.numel():
+        nv.louvain_apply(nodes, state.target, G.k, state.comm, state.tot, state.size, state.moved)
 
 
 def sweep(G, state, gamma=1.0):
@@ -310,9 +315,10 @@ def aggregate(G, comm):
     return LevelGraph(rowptr, col.contiguous(), w, loop), cmap
 
 
-def run_level(G, gamma, max_sweeps):
-    """One level from singletons: (state, the moved history)."""
-    state = singletons(G)
+def run_level(G, gamma, max_sweeps, comm0=None):
+    """The sweeps of one level from the partition comm0 (None: singletons) until nothing moves or the run stalls: (state, the moved
+    history)."""
+    state = singletons(G) if comm0 is None else state_of(G, comm0)
     history = []
     for _ in range(max_sweeps):
         history.append(sweep(G, state, gamma))
@@ -369,15 +375,26 @@ def louvain(embeddings, labels=None, resolution=1.0, n_neighbors=15, max_levels=
 
 def louvain_checked(embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol, return_graph=False, device='cuda'):
     """`louvain` behind its argument checks: the arguments are what `check_louvain` returned."""
+    return pooled_run('louvain', communities, run_summary, embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol,
+                      return_graph, device)
+
+
+def run_summary(out, *rest):
+    """`louvain_summary` of the dict of `communities`."""
+    return louvain_summary(out['clusters'], out['sizes'], out['modularity'], out['levels'], *rest)
+
+
+def pooled_run(what, run, summary, embeddings, labels, resolution, n_neighbors, max_levels, max_sweeps, tol, return_graph, device):
+    """The front end of `louvain` and `leiden.leiden`: the pooled cells, their fuzzy graph, `run` (a `communities`) on it, the two
+    contingency tables of its clusters and `summary` of it all."""
     from .spectral import build_graph
     n_cells = [_n_rows(e) for e in embeddings]
-    mod, lcode, classes = pooled_codes(n_cells, labels, 'louvain')
-    xs, x = _pool(embeddings, device, 'louvain')
+    mod, lcode, classes = pooled_codes(n_cells, labels, what)
+    xs, x = _pool(embeddings, device, what)
     G = build_graph(x, n_neighbors, device)
-    out = communities(G, resolution, max_levels, max_sweeps, tol)
+    out = run(G, resolution, max_levels, max_sweeps, tol)
     k = len(out['sizes'])
     table_mod = contingency(out['clusters'], mod, k, len(xs), device=x.device)
     table_lab = None if lcode is None else contingency(out['clusters'], lcode, k, len(classes), device=x.device)
     graph = G.to_scipy() if return_graph else None
-    return louvain_summary(out['clusters'], out['sizes'], out['modularity'], out['levels'], n_cells, table_mod, table_lab, classes,
-                           resolution, n_neighbors, G.col.numel(), graph)
+    return summary(out, n_cells, table_mod, table_lab, classes, resolution, n_neighbors, G.col.numel(), graph)

@@ -136,6 +136,43 @@ def test_cut_and_refine_equal_the_restatement_in_every_target(jld, name):
         assert 0 < 5 * inside < lens[0] and taken[1] == 1                     # most of the hub's entries are filtered out
 
 
+# (graph, what is wrong, the (short, long, global) counts the hub is listed under, the flag bit)
+REFUSALS = (('star65', 'bin', (1, 0, 0), 1), ('star65', 'comm', (0, 1, 0), 2), ('star2049', 'table', (0, 0, 1), 4))
+
+
+@pytest.mark.parametrize('name, what, counts, bit', REFUSALS)
+def test_refine_refuses_a_row_it_cannot_take(jld, name, what, counts, bit):
+    """The hub, alone in its part, alone in a hand-made node list: listed in the short bin, with its community out of range, and
+    with a table of too few slots.  The flag names the reason, the hub stays alone and nothing else is written: the row is never
+    walked."""
+    from jamie_amd import _native as nv
+    from jamie_amd import louvain as jlv
+    G, g, comm = level_case(name)
+    n, hub, dev = g['n'], 0, G.col.device
+    state = jlv.state_of(G, comm)
+    if what == 'comm':
+        state.comm[hub] = n
+    R = jld.start(G)
+    R.target.fill_(-7)
+    nodes = torch.tensor([hub], dtype=torch.int32, device=dev)
+    slot_off = torch.tensor([0, 2048], dtype=torch.int64, device=dev) if what == 'table' else None       # the row needs 8192
+    ws = torch.full((12 * 2048,), 0x55, dtype=torch.uint8, device=dev)
+    held = (state.comm, state.tot, R.ref, R.rtot, R.rsize, R.cut)
+    before = [t.clone() for t in held]
+    nv.leiden_refine(G.rowptr, G.col, G.w, G.k, state.comm, state.tot, R.ref, R.rtot, R.rsize, R.cut, 1.0, G.two_m, nodes, counts,
+                     slot_off, ws, R.target, R.flag)
+    got, flag = R.target.cpu().numpy(), int(R.flag.item())
+    print(f'{name}, {what}: a row of {int(G.lens[hub])} entries listed as {counts}: flag {flag}, target of the hub {got[hub]}, '
+          f'{int((got[1:] != -7).sum())} other targets written')
+    assert flag == bit
+    assert got[hub] == hub and np.all(got[1:] == -7)
+    assert all(torch.equal(a, b) for a, b in zip(before, held))
+    if what == 'table':                                                       # the cleared table: no slot was claimed
+        assert int(ws[:8 * 2048].view(torch.int64).abs().sum()) == 0 and bool((ws[8 * 2048:].view(torch.int32) == -1).all())
+    else:
+        assert bool((ws == 0x55).all())
+
+
 @pytest.mark.parametrize('name', (130, 600, 'hub', 'star65', 'star2049', 'filtered', 'heavy', 'ring', 'empty', 'chain', 'stuck'))
 def test_apply_keeps_the_tables_exact_after_every_subsweep(jld, name):
     from jamie_amd import louvain as jlv

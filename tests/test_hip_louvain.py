@@ -133,6 +133,39 @@ def test_move_equals_the_restatement_in_every_target(jlv, name):
         assert state.target.cpu().numpy().tolist() == [0, 0, 2, 2]
 
 
+# (graph, what is wrong, the (short, long, global) counts the hub is listed under, the flag bit)
+REFUSALS = (('star65', 'bin', (1, 0, 0), 1), ('star65', 'comm', (0, 1, 0), 2), ('star2049', 'table', (0, 0, 1), 4))
+
+
+@pytest.mark.parametrize('name, what, counts, bit', REFUSALS)
+def test_move_refuses_a_row_it_cannot_take(jlv, name, what, counts, bit):
+    """The hub alone in a hand-made node list: listed in the short bin, with its community out of range, and with a table of
+    too few slots.  The flag names the reason, the hub stays where it is and nothing else is written: the row is never walked."""
+    from jamie_amd import _native as nv
+    G, g = level_pair(jlv, name)
+    n, hub, dev = g['n'], 0, G.col.device
+    state = jlv.singletons(G)
+    if what == 'comm':
+        state.comm[hub] = n
+    state.target.fill_(-7)
+    nodes = torch.tensor([hub], dtype=torch.int32, device=dev)
+    slot_off = torch.tensor([0, 2048], dtype=torch.int64, device=dev) if what == 'table' else None       # the row needs 8192
+    ws = torch.full((12 * 2048,), 0x55, dtype=torch.uint8, device=dev)
+    before = [t.clone() for t in (state.comm, state.tot, state.size)]
+    nv.louvain_move(G.rowptr, G.col, G.w, G.k, state.comm, state.tot, state.size, 1.0, G.two_m, nodes, counts, slot_off, ws,
+                    state.target, state.flag)
+    got, flag = state.target.cpu().numpy(), int(state.flag.item())
+    print(f'{name}, {what}: a row of {int(G.lens[hub])} entries listed as {counts}: flag {flag}, target of the hub {got[hub]}, '
+          f'{int((got[1:] != -7).sum())} other targets written')
+    assert flag == bit
+    assert got[hub] == int(before[0][hub]) and np.all(got[1:] == -7)
+    assert all(torch.equal(a, b) for a, b in zip(before, (state.comm, state.tot, state.size)))
+    if what == 'table':                                                       # the cleared table: no slot was claimed
+        assert int(ws[:8 * 2048].view(torch.int64).abs().sum()) == 0 and bool((ws[8 * 2048:].view(torch.int32) == -1).all())
+    else:
+        assert bool((ws == 0x55).all())
+
+
 @pytest.mark.parametrize('name', (130, 600, 'hub', 'star2049', 'heavy', 'ring', 'pairs', 'empty'))
 def test_apply_and_sweep_keep_the_tables_exact(jlv, name):
     G, g = level_pair(jlv, name)

@@ -40,8 +40,11 @@ def test_symbols_are_declared_and_exported():
     lib = nv.load()
     for s in SYMBOLS:
         assert hasattr(lib, s)
-    src = open(os.path.join(ROOT, 'jamie_amd', 'csrc', 'leiden.hip')).read()
-    assert f'LD_SHORT_MAX = {vu.SHORT_MAX};' in src and f'LD_LONG_MAX = {vu.LONG_MAX};' in src
+    csrc = os.path.join(ROOT, 'jamie_amd', 'csrc')
+    src = open(os.path.join(csrc, 'community_rows.h')).read()
+    assert f'CR_SHORT_MAX = {vu.SHORT_MAX};' in src and f'CR_LONG_MAX = {vu.LONG_MAX};' in src
+    own = open(os.path.join(csrc, 'leiden.hip')).read()                      # the one pair of bin constants is the header's
+    assert 'community_rows.h' in own and 'SHORT_MAX =' not in own and 'LONG_MAX =' not in own
 
 
 def test_leiden_kernels_use_no_scratch():

@@ -58,9 +58,12 @@ def test_symbols_are_declared_and_exported():
     assert nv.louvain_workspace([2049]) == 12 * 8192 and nv.louvain_workspace([3, 5000]) == 12 * (8 + 16384)
     assert nv.louvain_workspace([-1]) == 0 and nv.louvain_workspace([]) == 0
     assert [jlv.table_slots(v) for v in (0, 1, 3, 2047, 2049, 5000)] == [2, 4, 8, 4096, 8192, 16384]
-    src = open(os.path.join(ROOT, 'jamie_amd', 'csrc', 'louvain.hip')).read()
-    assert f'LV_SHORT_MAX = {jlv.SHORT_MAX};' in src and f'LV_LONG_MAX = {jlv.LONG_MAX};' in src
+    csrc = os.path.join(ROOT, 'jamie_amd', 'csrc')
+    src = open(os.path.join(csrc, 'community_rows.h')).read()
+    assert f'CR_SHORT_MAX = {jlv.SHORT_MAX};' in src and f'CR_LONG_MAX = {jlv.LONG_MAX};' in src
     assert (jlv.SHORT_MAX, jlv.LONG_MAX) == (vu.SHORT_MAX, vu.LONG_MAX)
+    own = open(os.path.join(csrc, 'louvain.hip')).read()                     # the one pair of bin constants is the header's
+    assert 'community_rows.h' in own and 'SHORT_MAX =' not in own and 'LONG_MAX =' not in own
     # the refusals come before any launch: no device is needed to see them
     p = [8] * 3
     assert lib.jamie_louvain_move(*p, 0, 4, 8, 8, 8, 8, 1.0, 1 << 52, 8, 4, 0, 0, None, 0, None, 0, 16, 8, None) != 0

@@ -43,7 +43,7 @@ def child_case(N, L, a, say):
     nnz = int(G.col.numel())
     LG = jlv.level_graph(G)
     bins = LG.plan()['counts'].sum(axis=0).tolist()
-    moved, history = jld.move_phase(LG, None, 1.0, 32)
+    moved, history = jlv.run_level(LG, 1.0, 32)
     n_comm = int((moved.size > 0).sum().item())
     R = jld.start(LG)
     state = jlv.singletons(LG)
